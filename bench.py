@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the content engine (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, packs W warm-up steps and K timed steps, and prints the JSON line (ms_per_step = one timed pack step).
+--dump-outputs DIR also writes what the last timed pack returned (see dump_outputs).  --full adds everything else the benchmark
+measures or checks: the unpack rate and the bit-exact round trip, per-kernel times and rooflines, host_path, cpu_baseline and the
+ratio against libzstd.
 
 N > 1: one rank per GPU under torch.distributed.run.  Started that way (WORLD_SIZE set) this process IS a rank; started plainly
 (`python bench.py --gpus 8`) it launches `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...
@@ -14,11 +19,11 @@ workload: BASELINE.json configs[1]/[2] -- 10 000 x 1 MiB synthetic entries per G
           random round-robin); `--entries` scales it down for quick runs.
           --config c4: configs[3] shape (4 MiB frames of the lz stream, level 9), --config c5: configs[4] shape (64 KiB .. 16 MiB
           log-uniform sizes, level 3) -- whatever count fits one GPU; their lines are kept under profiles/.
-step    : one pack pass over the whole batch (timed region 1), and one unpack pass over its output (region 2).
+step    : one pack pass over the whole batch (timed region 1); --full: and one unpack pass over its output (region 2).
 scaling : weak -- the global entry list is dealt to the ranks by the same sharder the product uses (zarc::ShardedEncoder: index mod
           G for equal sizes, greedy by bytes otherwise; zarc_amd/shard.py), every rank packs its share; no collective on the data
           path; only the timing barrier / max-over-ranks uses torch.distributed (RCCL).
-extras  : host_path (PCIe-inclusive rates through the host-pointer entry points, pageable and pinned), unpack_roofline,
+extras  : (--full) host_path (PCIe-inclusive rates through the host-pointer entry points, pageable and pinned), unpack_roofline,
           cpu_baseline (the reference's CPU path, C driver tests/support/cpu_baseline.c, 1 thread and all host cores).
 """
 import argparse
@@ -36,6 +41,9 @@ sys.path.insert(0, ROOT)
 
 GIB = float(1 << 30)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_ENTRIES = 65536          # --dump-outputs: per-entry results of at most this many entries (35 values each)
+DUMP_FRAME_BYTES = 8 << 20    # --dump-outputs: frame bytes written, as float32 (32 MB); the whole dump stays under 64 MB
+DUMP_SEED = 20261016
 
 
 def aggregate(local_seconds, local_units, dist=None, device=None):
@@ -213,6 +221,36 @@ def host_path(eng, _lib, torch, d_src, off, lens, n_host, size):
     return out
 
 
+def dump_sample(sizes, bound):
+    """--dump-outputs' two seeded samples, chosen from the entry count and sizes alone (so two builds dump the same entries): the
+    entries whose per-entry results are written (all, or DUMP_ENTRIES of them) and those whose frames are written (their size bounds
+    fit in DUMP_FRAME_BYTES), both in index order."""
+    n = len(sizes)
+    rng = np.random.default_rng(DUMP_SEED)
+    sel = np.arange(n) if n <= DUMP_ENTRIES else np.sort(rng.choice(n, DUMP_ENTRIES, replace=False))
+    framed, room = [], DUMP_FRAME_BYTES
+    for i in rng.permutation(n)[:4096]:
+        b = int(bound(int(sizes[i])))
+        if b <= room:
+            framed.append(int(i))
+            room -= b
+    return sel, sorted(framed)
+
+
+def dump_outputs(path, eng, d_dst, sizes, doff, dlen, dig, st):
+    """--dump-outputs: what the last timed pack handed its caller, as .npy files of float64 / float32 (every value exact):
+    frame_offset, frame_len (float64), digest (BLAKE3, 32 bytes per entry), status of dump_sample's first sample, and frame_bytes:
+    the frames of its second sample, concatenated."""
+    sel, framed = dump_sample(sizes, eng.bound)
+    frames = [eng.d2h(d_dst + int(doff[i]), int(dlen[i])) for i in framed]
+    os.makedirs(path, exist_ok=True)
+    arrays = {"frame_offset": doff[sel].astype(np.float64), "frame_len": dlen[sel].astype(np.float64),
+              "digest": dig[sel].astype(np.float32), "status": st[sel].astype(np.float32),
+              "frame_bytes": np.concatenate(frames).astype(np.float32) if frames else np.zeros(0, np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def launch_command(n, argv, port):
     """The command a plain `python bench.py --gpus N ...` starts as a child: one rank per GPU of this node over RCCL."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
@@ -241,10 +279,13 @@ def main():
     ap.add_argument("--gib", type=float, default=32.0, help="c4 / c5: uncompressed GiB per GPU")
     ap.add_argument("--entries", type=int, default=None, help="entries per GPU (default: BASELINE configs[1]'s 10000; --config small: 1000000)")
     ap.add_argument("--size", type=int, default=1 << 20, help="bytes per entry (BASELINE configs[1]: 1 MiB)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed pack returned as DIR/<name>.npy (rank 0's share)")
+    ap.add_argument("--full", action="store_true", help="also measure unpack (rate, bit-exact round trip), per-kernel times and rooflines, "
+                                                         "host_path, cpu_baseline and the ratio against libzstd")
     ap.add_argument("--cpu-sample", type=int, default=1024, help="entries timed on one host thread for cpu_baseline (rank 0, N=1)")
     ap.add_argument("--host-entries", type=int, default=8192, help="entries (of the resident batch) sent through the host-pointer entry points")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-path", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-host-path", action="store_true", help="--full without host_path")
     ap.add_argument("--dec-groups", type=int, default=0, help="diagnostics: ZARC_GPU_PX_DEC_GROUPS (0 = the engine decides by the batch's shape)")
     ap.add_argument("--level", type=int, default=None, help="compression level instead of the configuration's (c2 / c5 / small: 3, c4: 9); the metric then names it")
     ap.add_argument("--kind", type=int, default=-1, help="diagnostics: use one corpus kind for every entry (default: round-robin)")
@@ -257,19 +298,24 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: start the ranks ourselves, as a child (this process has not imported torch nor touched HIP)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     if args.gpus != world:
         sys.exit("bench.py: --gpus %d but WORLD_SIZE is %d (launcher and flag disagree)" % (args.gpus, world))
-    import torch
-    dist = None
+    # torch is the multi-process plumbing (and host_path's buffers): a plain single-process run needs none of it, every engine call
+    # used here returns after its work is done
+    torch = dist = device = None
+    if args.full or world > 1 or "RANK" in os.environ:
+        import torch
+        device = torch.device("cuda", local_rank)
     if world > 1 or "RANK" in os.environ:  # under torchrun always go through RCCL, even with one rank
         import torch.distributed as dist_mod
         torch.cuda.set_device(local_rank)
         dist_mod.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
         dist = dist_mod
-    device = torch.device("cuda", local_rank)
 
     from zarc_amd import Engine, _lib
     sizes, index, kind, level, desc, n_global = workload(args, rank, world)
@@ -288,7 +334,7 @@ def main():
     cap = sum(bound_of[s] for s in sizes)
     d_src = eng.malloc(total_in + _lib.PAD)
     d_dst = eng.malloc(cap + _lib.PAD)
-    d_out = eng.malloc(total_in + _lib.PAD)
+    d_out = eng.malloc(total_in + _lib.PAD) if args.full else None
     # corpus entry of global index g is generated as corpus index g (any rank can generate any entry independently); c4 cuts ONE lz
     # stream per frame index the same way
     idx = np.array(index, dtype=np.int64)
@@ -299,7 +345,8 @@ def main():
     def barrier():
         if dist is not None:
             dist.barrier()
-        torch.cuda.synchronize(device)
+        if torch is not None:
+            torch.cuda.synchronize(device)
 
     # ---------------- pack ----------------
     for _ in range(args.warmup):
@@ -309,34 +356,48 @@ def main():
     k_ms = np.zeros(_lib.T_DEC_FRAMES + 1)
     for _ in range(args.steps):
         doff, dlen, dig, st = eng.pack_device(d_src, off, lens, d_dst, cap)   # synchronous at the ABI
-        k_ms += np.array([eng.kernel_ms(i) for i in range(_lib.T_DEC_FRAMES + 1)])
+        if args.full:
+            k_ms += np.array([eng.kernel_ms(i) for i in range(_lib.T_DEC_FRAMES + 1)])
     barrier()
     t_pack = time.perf_counter() - t0
     assert (st == 0).all()
-    k_ms /= max(args.steps, 1)
+    k_ms /= args.steps
     raw_bytes = float(lens.sum())
     comp_bytes = float(dlen.sum())
-
-    # ---------------- unpack ----------------
-    for _ in range(args.warmup):
-        dig2, st2 = eng.unpack_device(d_dst, doff, dlen, d_out, off, lens, expect=dig)
-    barrier()
-    t0 = time.perf_counter()
-    u_ms = np.zeros(_lib.T_DEC_FRAMES + 1)
-    for _ in range(args.steps):
-        dig2, st2 = eng.unpack_device(d_dst, doff, dlen, d_out, off, lens, expect=dig)
-        u_ms += np.array([eng.kernel_ms(i) for i in range(_lib.T_DEC_FRAMES + 1)])
-    barrier()
-    t_unpack = time.perf_counter() - t0
-    u_ms /= max(args.steps, 1)
-    ok = bool((st2 == 0).all() and (dig2 == dig).all())      # bit-exact round trip: same BLAKE3 on both sides
-
     tp, units = aggregate(t_pack, raw_bytes * args.steps, dist, device)
-    tu, _ = aggregate(t_unpack, raw_bytes * args.steps, dist, device)
     pack_gibs = units / tp / GIB
-    unpack_gibs = units / tu / GIB
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, d_dst, lens, doff, dlen, dig, st)
+
+    ok = True
+    if args.full:
+        # ---------------- unpack ----------------
+        for _ in range(args.warmup):
+            dig2, st2 = eng.unpack_device(d_dst, doff, dlen, d_out, off, lens, expect=dig)
+        barrier()
+        t0 = time.perf_counter()
+        u_ms = np.zeros(_lib.T_DEC_FRAMES + 1)
+        for _ in range(args.steps):
+            dig2, st2 = eng.unpack_device(d_dst, doff, dlen, d_out, off, lens, expect=dig)
+            u_ms += np.array([eng.kernel_ms(i) for i in range(_lib.T_DEC_FRAMES + 1)])
+        barrier()
+        t_unpack = time.perf_counter() - t0
+        u_ms /= args.steps
+        ok = bool((st2 == 0).all() and (dig2 == dig).all())      # bit-exact round trip: same BLAKE3 on both sides
+        tu, _ = aggregate(t_unpack, raw_bytes * args.steps, dist, device)
 
     if rank == 0:
+        line = {
+            "metric": "uncompressed GiB/s (pack) at zstd -%d" % level, "value": round(pack_gibs, 3), "unit": "GiB/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(tp / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "config": {"workload": desc, "entries_per_gpu": n, "entries_total": n_global, "entry_bytes": args.size if args.config == "c2" else "mixed" if args.config in ("c5", "small") else 4 << 20,
+                       "level": level, "kinds": "text/records/lz/random round-robin" if kind < 0 else "kind %d" % kind,
+                       "parallelism": "frames dealt to %d GPU(s) by the product's sharder (index mod G / greedy by bytes), no collective" % world},
+            "ratio": round(raw_bytes / comp_bytes, 4),
+            "library_sha16": lib_sha16(eng.lib_path), "source_sha16": src_sha16(),
+        }
+    if rank == 0 and args.full:
         # roofline of the dominant kernel of the headline (pack) path: the match finder.  Algorithmic bytes per
         # frame = N + C + 32; duration from HIP events on the engine's stream.
         names = {_lib.T_BLAKE3: "blake3", _lib.T_XXH64: "xxh64", _lib.T_MATCH: "zge_match", _lib.T_ENTROPY: "zge_entropy",
@@ -368,16 +429,9 @@ def main():
                 traffic_src = "profiles/r04_bench_pmc_summary.json (same kernel sources %s, same workload)" % pmc["src_sha16"]
             else:
                 traffic_src = "none: profiles/r04_bench_pmc_summary.json is of another build or workload"
-        line = {
-            "metric": "uncompressed GiB/s (pack) at zstd -%d" % level, "value": round(pack_gibs, 3), "unit": "GiB/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(tp / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": desc, "entries_per_gpu": n, "entries_total": n_global, "entry_bytes": args.size if args.config == "c2" else "mixed" if args.config in ("c5", "small") else 4 << 20,
-                       "level": level, "kinds": "text/records/lz/random round-robin" if kind < 0 else "kind %d" % kind,
-                       "parallelism": "frames dealt to %d GPU(s) by the product's sharder (index mod G / greedy by bytes), no collective" % world},
-            "unpack_gibs": round(unpack_gibs, 3), "unpack_ms_per_step": round(tu / args.steps * 1e3, 3),
+        line.update({
+            "unpack_gibs": round(units / tu / GIB, 3), "unpack_ms_per_step": round(tu / args.steps * 1e3, 3),
             "roundtrip_bit_exact": ok,
-            "ratio": round(raw_bytes / comp_bytes, 4),
             "kernel_ms": {names[i]: round(float(k_ms[i]), 3) for i in names},
             "unpack_kernel_ms": {"zstd_decode": round(float(u_ms[_lib.T_DECODE]), 3), "zdec_seqs": round(float(u_ms[_lib.T_DEC_SEQS]), 3),
                                  "zdec_literals": round(float(u_ms[_lib.T_DEC_LITS]), 3), "zstd_frames": round(float(u_ms[_lib.T_DEC_FRAMES]), 3),
@@ -388,8 +442,7 @@ def main():
             "unpack_roofline": {"bound": "hbm", "kernel": unames[udom], "achieved": round(u_achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                                 "frac": round(u_achieved / HBM_PEAK_GBS, 5), "traffic": u_traffic,
                                 "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": round(float(u_ms[udom]), 3)},
-            "library_sha16": lib_sha16(eng.lib_path), "source_sha16": src_sha16(),
-        }
+        })
         if world == 1 and args.config == "c2" and not args.no_host_path:
             nh = min(args.host_entries, n)
             line["host_path"] = host_path(eng, _lib, torch, d_src, off, lens, nh, args.size)
@@ -414,9 +467,11 @@ def main():
                     ours = float(dlen[:ref_n].sum())
                     line["ratio_vs_reference"] = round(ref_comp / ours, 4)   # >= 0.95 required (within 5 % of libzstd -3)
                     line["ratio_reference"] = "%s -%d on the first %d entries" % (ref_name, level, ref_n)
+    if rank == 0:
         print(json.dumps(line))
     for p in (d_src, d_dst, d_out):
-        eng.free(p)
+        if p is not None:
+            eng.free(p)
     eng.close()
     if dist is not None:
         dist.destroy_process_group()

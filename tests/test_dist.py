@@ -185,6 +185,46 @@ def test_bench_workload_gives_every_rank_the_same_mix():
         assert sorted(seen) == list(range(1000 * world))
 
 
+def test_bench_dump_outputs_are_what_the_pack_returned(emu_engine, oracle, corpus, tmp_path):
+    """`bench.py --dump-outputs` on the emulator build: float arrays holding exactly what pack_device returned (offsets, lengths,
+    digests, statuses, the sampled frames, which decode to their entries); on a large batch the samples stay within 64 MB and follow
+    from the sizes alone."""
+    import numpy as np
+    import bench
+    from zarc_amd import _lib
+    sizes = [70000, 3000, 0, 140000, 65536, 131072, 5, 90001]
+    ents = [corpus.entry(600 + i, n, -1) for i, n in enumerate(sizes)]
+    lens = np.array(sizes, dtype=np.uint64)
+    off = np.concatenate([[0], np.cumsum((lens + np.uint64(15)) // np.uint64(16) * np.uint64(16))]).astype(np.uint64)
+    cap = sum(int(emu_engine.bound(s)) for s in sizes)
+    d_src, d_dst = emu_engine.malloc(int(off[-1]) + _lib.PAD), emu_engine.malloc(cap + _lib.PAD)
+    try:
+        for o, e in zip(off, ents):
+            if e:
+                emu_engine.h2d(d_src + int(o), e)
+        doff, dlen, dig, st = emu_engine.pack_device(d_src, off[:-1], lens, d_dst, cap)
+        bench.dump_outputs(str(tmp_path), emu_engine, d_dst, sizes, doff, dlen, dig, st)
+        frames = [bytes(emu_engine.d2h(d_dst + int(doff[i]), int(dlen[i]))) for i in range(len(sizes))]
+    finally:
+        emu_engine.free(d_src)
+        emu_engine.free(d_dst)
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["digest", "frame_bytes", "frame_len", "frame_offset", "status"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert (got["frame_offset"] == doff).all() and (got["frame_len"] == dlen).all() and (got["digest"] == dig).all()
+    assert (st == 0).all() and (got["status"] == 0).all()
+    assert [list(s) for s in bench.dump_sample(sizes, emu_engine.bound)] == [list(range(len(sizes)))] * 2
+    assert got["frame_bytes"].astype(np.uint8).tobytes() == b"".join(frames)
+    for raw, frame, d in zip(ents, frames, dig):
+        assert oracle.zstd_decode(frame, len(raw))[1] == raw and bytes(d) == oracle.blake3(raw)
+    big = [1 << 20] * 200000 + [4 << 20] * 1000
+    sel, framed = bench.dump_sample(big, emu_engine.bound)
+    assert len(sel) == bench.DUMP_ENTRIES and list(sel) == sorted(set(sel)) and framed == sorted(set(framed))
+    assert sum(int(emu_engine.bound(big[i])) for i in framed) <= bench.DUMP_FRAME_BYTES
+    assert len(sel) * (8 + 8 + 4 * 32 + 4) + 4 * bench.DUMP_FRAME_BYTES <= 64 << 20
+    assert [list(s) for s in bench.dump_sample(big, emu_engine.bound)] == [list(sel), framed]
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus N` without a launcher must start N ranks itself, as a child process (the driver's SCALE run may call
     it either way).  The command is torch.distributed.run on 127.0.0.1; on this GPU-less box the ranks then fail loudly at

@@ -321,16 +321,16 @@ def test_gpu_two_devices_pack_and_unpack(engine, oracle, corpus):
         e.close()
 
 
-def _bench(args, launcher):
+def _bench(args, launcher, full=True):
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    small = ["--entries", "64", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-host-path"]
+    small = ["--entries", "64", "--steps", "1", "--warmup", "1"] + (["--full", "--no-cpu-baseline", "--no-host-path"] if full else [])
     pre = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29631"] if launcher else [sys.executable]
-    r = subprocess.run(pre + [os.path.join(root, "bench.py")] + args + small, env=env, capture_output=True, timeout=900)
+    r = subprocess.run(pre + [os.path.join(root, "bench.py")] + small + args, env=env, capture_output=True, timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     return json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
 
@@ -340,6 +340,33 @@ def test_gpu_bench_under_the_launcher():
     max-over-ranks -- the code path of every multi-GPU run)."""
     line = _bench(["--gpus", "1"], launcher=True)
     assert line["n_gpus"] == 1 and line["roundtrip_bit_exact"] and line["value"] > 0
+
+
+def test_gpu_bench_plain_run_and_its_outputs(tmp_path, oracle, corpus):
+    """A plain `bench.py --gpus 1` run carries the headline only (--full adds unpack and the rest) and times --steps steps;
+    --dump-outputs writes what the last timed pack returned: float arrays, 64 MB at most, whose digests and frames are those of the
+    corpus entries the sample names."""
+    import os
+    import bench
+    out = tmp_path / "dump"
+    line = _bench(["--gpus", "1", "--steps", "2", "--dump-outputs", str(out)], launcher=False, full=False)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "GiB/s" and line["dtype"] == "u8"
+    assert "unpack_gibs" not in line and "roofline" not in line and "cpu_baseline" not in line
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert sorted(got) == ["digest", "frame_bytes", "frame_len", "frame_offset", "status"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    sizes = [1 << 20] * 64
+    sel, framed = bench.dump_sample(sizes, _lib.load().zarc_gpu_bound)
+    assert list(sel) == list(range(64)) and framed and (got["status"] == 0).all()
+    frames = got["frame_bytes"].astype(np.uint8).tobytes()
+    pos = 0
+    for i in framed:
+        raw = corpus.entry(i, sizes[i], -1)
+        n = int(got["frame_len"][i])
+        assert bytes(got["digest"][i].astype(np.uint8)) == oracle.blake3(raw)
+        assert oracle.zstd_decode(frames[pos:pos + n], len(raw))[1] == raw
+        pos += n
+    assert pos == len(frames)
 
 
 def test_gpu_bench_starts_its_own_ranks(engine):

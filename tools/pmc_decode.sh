@@ -2,7 +2,7 @@
 # SQ counters for the decoder kernels (separate passes; program directly after --)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_decode; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 export ZARC_GPU_DEC_SIDE=0
-CMD="python3 $R/bench.py --entries ${N:-4096} --steps 1 --warmup 1 --no-cpu-baseline"
+CMD="python3 $R/bench.py --full --entries ${N:-4096} --steps 1 --warmup 1 --no-cpu-baseline"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" \
            "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM SQ_WAIT_INST_LDS SQ_INSTS_SMEM SQ_IFETCH" \

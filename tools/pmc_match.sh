@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ / cache counters for the encoder kernels (separate passes; no tracing flags besides kernel names)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/pmc_match; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
-CMD="python3 $R/bench.py --entries 1024 --steps 1 --warmup 1 --no-cpu-baseline"
+CMD="python3 $R/bench.py --full --entries 1024 --steps 1 --warmup 1 --no-cpu-baseline"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" \
            "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_LDS" \

@@ -5,7 +5,7 @@
 TAG=${1:-r01}; N=${2:-2048}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/prof_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-CMD="python3 $R/bench.py ${BENCH_ARGS:---entries $N} --steps 2 --warmup 1 --no-cpu-baseline --no-host-path"
+CMD="python3 $R/bench.py --full ${BENCH_ARGS:---entries $N} --steps 2 --warmup 1 --no-cpu-baseline --no-host-path"
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- $CMD > $O/trace.log 2>&1; echo "trace rc=$?"
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- $CMD > $O/fetch.log 2>&1; echo "fetch rc=$?"
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -- $CMD > $O/write.log 2>&1; echo "write rc=$?"

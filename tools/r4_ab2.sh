@@ -1,9 +1,9 @@
 #!/bin/bash
 # round 4: how many waves does the shared-table kernel turn down at configs[1]?  then SQ counters of the decoder kernels
 cd $GRAFT_REPO_ROOT; O=gpurun_out
-ZARC_GPU_LIB=$PWD/zarc_amd/libzarc_gpu_diag.so ZARC_GPU_DEC_STATS=1 timeout -k 10 300 python bench.py --no-cpu-baseline --no-host-path --steps 1 --warmup 1 2>&1 >/dev/null | grep -E "zdec_seqs|zstd_decode" | sort | uniq -c
+ZARC_GPU_LIB=$PWD/zarc_amd/libzarc_gpu_diag.so ZARC_GPU_DEC_STATS=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-host-path --steps 1 --warmup 1 2>&1 >/dev/null | grep -E "zdec_seqs|zstd_decode" | sort | uniq -c
 R=$GRAFT_REPO_ROOT; P=$R/gpurun_out/r4_pmc_dec; mkdir -p $P; cd /tmp; export TMPDIR=/tmp
-CMD="python3 $R/bench.py --entries 10000 --steps 1 --warmup 1 --no-cpu-baseline --no-host-path"
+CMD="python3 $R/bench.py --full --entries 10000 --steps 1 --warmup 1 --no-cpu-baseline --no-host-path"
 i=0
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU" \
            "SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_SMEM"; do

@@ -4,7 +4,7 @@
 TAG=$1; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/tl_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-path "$@" > $O/log.txt 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-path "$@" > $O/log.txt 2>&1
 python3 - <<PY
 import csv, glob
 ev = []

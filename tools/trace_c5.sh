@@ -2,7 +2,7 @@
 # kernel timeline (rocprofv3 --kernel-trace) of one configs[4]-shape pack + unpack: tools/trace_c5.sh lib tag
 LIB=$1; TAG=${2:-c5}; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/trace_$TAG; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-ZARC_GPU_LIB=$R/$LIB timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O -- python3 $R/bench.py --config c5 --gib 24 --steps 1 --warmup 1 --no-cpu-baseline --no-host-path > $O/log.txt 2>&1
+ZARC_GPU_LIB=$R/$LIB timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O -- python3 $R/bench.py --full --config c5 --gib 24 --steps 1 --warmup 1 --no-cpu-baseline --no-host-path > $O/log.txt 2>&1
 python3 - <<PY
 import csv, glob
 rows = []
