@@ -93,11 +93,17 @@ enum {
     ZARC_GPU_PX_COPY_THREADS = 9004, /* host threads that fill / drain the pinned staging ring (default 8)                                          */
     ZARC_GPU_PX_DEC_GROUPS = 9005,   /* unpack: frames are dealt by descending size into this many groups whose stages overlap (1..4; 0 = by the
                                         batch: 2 when its largest frame has 4 MiB and more and four times the mean size, else 1)                                                    */
-    ZARC_GPU_PX_ZERO_COPY = 9006     /* host-pointer entry points: when every buffer of a chunk is page-locked memory the device can reach (hipHostMalloc /
+    ZARC_GPU_PX_ZERO_COPY = 9006,    /* host-pointer entry points: when every buffer of a chunk is page-locked memory the device can reach (hipHostMalloc /
                                         hipHostRegister by the caller, same HIP runtime) AND the buffers form runs -- contiguous in the caller's memory and in
                                         batch order -- of at least this many KiB on average, the DMA engines move them directly and the staging ring with its
                                         host memcpy pass is skipped.  Default 4096 (a DMA per small scattered buffer is slower than the ring); 0 = always stage.
                                         Ordinary (pageable) buffers are staged either way. */
+    /* UNLIKE THE IDS ABOVE THIS ONE CHANGES THE BYTES THAT COME OUT (every frame stays valid Zstandard of the same content). */
+    ZARC_GPU_PX_BLOCK_SPLIT = 9007   /* 0 (default): a block every 64 KiB and nowhere else.  1: a 64 KiB block is cut into up to 16 Zstandard blocks at sequence
+                                        boundaries where its literal statistics change, each with its own Huffman table and table modes (what libzstd 1.5 does
+                                        inside compress2).  Smaller frames on ELF / machine code / JSON, the same on text; zarc_gpu_bound() holds unchanged (a
+                                        block whose pieces would cost more than one raw block goes out as one).  Store mode ignores it.  Other values:
+                                        ZARC_GPU_E_PARAM. */
 };
 /* What the engine does with the libzstd ids (pack.rs:86-217 forwards them all):
  *   CompressionLevel  -131072..22 accepted; four finders (zarc_gpu_level_finder says which one a level runs):
@@ -137,15 +143,17 @@ int zarc_gpu_create(zarc_gpu_t **out, int device);
  * independent, so a caller that wants G devices opens G handles and deals its batch itself. */
 int zarc_gpu_device_count(void);
 void zarc_gpu_destroy(zarc_gpu_t *h);
-/* Sticky across batches, like Encoder::set_zstd_parameter.  Unknown ids -> ZARC_GPU_E_PARAM; ids libzstd
- * knows but the engine ignores (LDM, NbWorkers, ...) -> ZARC_GPU_E_UNSUPPORTED. */
+/* Sticky across batches, like Encoder::set_zstd_parameter.  Unknown ids -> ZARC_GPU_E_PARAM; ids libzstd knows but the
+ * engine cannot honour (NbWorkers, JobSize, OverlapLog, experimental ids) -> ZARC_GPU_E_UNSUPPORTED.  The search-effort
+ * and long-distance-matching ids are accepted and ADVISORY (see above; zarc_gpu_parameter_advisory). */
 int zarc_gpu_set_parameter(zarc_gpu_t *h, int param_id, int value);
 void zarc_gpu_get_params(const zarc_gpu_t *h, zarc_gpu_params *out);
 /* Encoder::enable_compression */
 void zarc_gpu_enable_compression(zarc_gpu_t *h, int compress);
-/* Worst-case frame size for an n-byte entry (all raw blocks): n + 3*max(1,ceil(n/65536)) + 18,
- * rounded up to ZARC_GPU_ALIGN.  The reference's Vec capacity rule (lowlevel_frames.rs:21) is smaller
- * than libzstd's own bound; this one never fails. */
+/* Worst-case frame size for an n-byte entry: n + 3*max(1,ceil(n/65536)) + 18, rounded up to ZARC_GPU_ALIGN.  The formula is
+ * the compressing encoder's worst case (every 64 KiB block raw, 3 bytes of header each, with or without
+ * ZARC_GPU_PX_BLOCK_SPLIT); store-mode frames have 131 072-byte raw blocks and a 14-byte header, which it covers as well.
+ * The reference's Vec capacity rule (lowlevel_frames.rs:21) is smaller than libzstd's own bound; this one never fails. */
 size_t zarc_gpu_bound(size_t n);
 const char *zarc_gpu_error_name(int code);         /* call-level codes (negative) */
 const char *zarc_gpu_frame_status_name(int status); /* per-frame status (>= 0)     */

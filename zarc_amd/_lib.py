@@ -25,6 +25,8 @@ P_ENABLE_LDM, P_LDM_HASH_LOG, P_LDM_MIN_MATCH, P_LDM_BUCKET_SIZE_LOG, P_LDM_HASH
 P_CONTENT_SIZE_FLAG, P_CHECKSUM_FLAG, P_DICT_ID_FLAG = 200, 201, 202
 # engine tuning (batching only; frames are identical for every value)
 PX_SCRATCH_MB, PX_STAGE_CHUNK, PX_STAGE_THREAD, PX_COPY_THREADS, PX_DEC_GROUPS, PX_ZERO_COPY = 9001, 9002, 9003, 9004, 9005, 9006
+# ... and the one engine switch that DOES change the frames: 1 = 64 KiB blocks are cut where their literal statistics change (default 0)
+PX_BLOCK_SPLIT = 9007
 # timers
 T_BLAKE3, T_XXH64, T_MATCH, T_ENTROPY, T_ASSEMBLE, T_DECODE, T_TOTAL, T_DEC_SEQS, T_DEC_LITS, T_DEC_FRAMES = range(10)
 

@@ -70,6 +70,9 @@ struct zarc_gpu {
     DevBuf d_cvs, d_cvs_tmp, d_digests, d_xxh, d_expect;
     // encoder
     DevBuf d_blocks, d_seq, d_lit, d_out, d_far, d_plan, d_groups;
+    DevBuf d_pblocks, d_zpieces; // block splitting: ZGE_SPLIT_K piece slots per parent block (records, placement)
+    DevBuf d_enc_err;           // one word the entropy stage raises when the table plan's size bound did not hold
+    int block_split = 0;        // ZARC_GPU_PX_BLOCK_SPLIT
     // decoder
     DevBuf d_declit, d_status, d_stored_ck;
     DevBuf d_slot_prefix, d_zblocks, d_nseq, d_fast, d_seqidx, d_seqs, d_ztables, d_litidx, d_lits, d_seqflag, d_totals, d_predef, d_longlist, d_longcnt; // decoder fast path (sequences decoded ahead)
@@ -439,6 +442,7 @@ int zarc_gpu_set_parameter(zarc_gpu_t *h, int id, int value)
         if (value < 0 || value > zarc_gpu::DEC_GROUPS) return ZARC_GPU_E_PARAM;
         h->dec_groups = value; return ZARC_GPU_OK;
     case ZARC_GPU_PX_ZERO_COPY: if (value < 0 || value > (1 << 20)) return ZARC_GPU_E_PARAM; h->zero_copy = value; return ZARC_GPU_OK;
+    case ZARC_GPU_PX_BLOCK_SPLIT: if (value != 0 && value != 1) return ZARC_GPU_E_PARAM; h->block_split = value; return ZARC_GPU_OK;
     case ZARC_GPU_P_CONTENT_SIZE_FLAG:
         if (value != 1) return ZARC_GPU_E_UNSUPPORTED; // frames always carry their content size
         return ZARC_GPU_OK;
@@ -641,7 +645,11 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
     HOST_PHASE(0); // checks, descriptor uploads, checksum + digest set-up
     const std::vector<uint32_t> order = order_by_size_desc(src_len, n);
     HOST_PHASE(1); // size ordering
-    auto per_block_of = [](uint32_t slot) { return (size_t)(zge_seq_stride(slot) * 8 + zge_lit_stride(slot) + zge_out_stride(slot) + sizeof(ZgeBlock) + sizeof(ZgePlan)); };
+    const bool split = h->block_split != 0; // blocks cut where their statistics change (zge_split.hip): ZGE_SPLIT_K piece slots per block
+    const size_t per_block_records = (sizeof(ZgeBlock) + sizeof(ZgePlan)) * (split ? 1 + ZGE_SPLIT_K : 1) + (split ? sizeof(ZgePiece) * ZGE_SPLIT_K : 0);
+    auto per_block_of = [per_block_records](uint32_t slot) { return (size_t)(zge_seq_stride(slot) * 8 + zge_lit_stride(slot) + zge_out_stride(slot)) + per_block_records; };
+    ZHIP(h->d_enc_err.reserve(16));
+    ZHIP(hipMemsetAsync(h->d_enc_err.p, 0, 4, h->stream));
     size_t budget = h->scratch_budget;
     if (!budget) {
         // up to 64 GiB of scratch (BASELINE configs[1] needs 46 GiB to run as ONE launch per kernel), at most 45 % of what is free
@@ -678,6 +686,10 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
         ZHIP(h->d_seq.reserve(nb * (size_t)zge_seq_stride(slot) * 8));
         ZHIP(h->d_lit.reserve(nb * (size_t)zge_lit_stride(slot)));
         ZHIP(h->d_out.reserve(nb * (size_t)zge_out_stride(slot)));
+        if (split) {
+            ZHIP(h->d_pblocks.reserve(nb * ZGE_SPLIT_K * sizeof(ZgeBlock)));
+            ZHIP(h->d_zpieces.reserve(nb * ZGE_SPLIT_K * sizeof(ZgePiece)));
+        }
         ZHIP(h->d_queue.reserve(256));
         int a, b, c, d;
         ZHIP(t.mark(&a));
@@ -748,7 +760,29 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
         ZHIP(t.mark(&b));
         {
             unsigned long long *const eprof = (P.dbg & 1024) ? (unsigned long long *)((char *)h->d_queue.p + 128) : (unsigned long long *)nullptr;
-            if (bp[1] - bp[0] > 1) {
+            if (split) {
+                // block splitting: the cut decision, then the same stage with a wave per parent that codes the parent's pieces one after
+                // the other; frames of one block keep the one-pass kernel, their pieces choose their tables alone
+                const size_t ns = nb * ZGE_SPLIT_K; // piece slots
+                hipLaunchKernelGGL(zarc_zge_split, dim3((unsigned)nb), dim3(64), 0, h->stream, (uint32_t)nb, slot, h->d_blocks.as<ZgeBlock>(), h->d_seq.as<uint64_t>(),
+                                   h->d_lit.as<uint8_t>(), h->d_pblocks.as<ZgeBlock>(), h->d_zpieces.as<ZgePiece>());
+                if (bp[1] - bp[0] > 1) {
+                    ZHIP(h->d_plan.reserve(ns * sizeof(ZgePlan)));
+                    std::vector<uint32_t> groups;
+                    for (size_t j = 0; j < m && bp[j + 1] - bp[j] > 1; j++)
+                        for (uint64_t g0 = bp[j]; g0 < bp[j + 1]; g0 += ZGE_TABLE_GROUP) groups.push_back((uint32_t)g0);
+                    if ((rc = upload_u32(h, h->d_groups, groups.data(), groups.size()))) return rc;
+                    hipLaunchKernelGGL(zarc_zge_entropy_p1_split, dim3((unsigned)nb), dim3(64), 0, h->stream, (uint32_t)nb, slot, h->d_pblocks.as<ZgeBlock>(),
+                                       h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof, h->d_plan.as<ZgePlan>(), h->d_zpieces.as<ZgePiece>());
+                    hipLaunchKernelGGL(zarc_zge_plan_split, dim3((unsigned)groups.size()), dim3(64), 0, h->stream, (uint32_t)nb, h->d_blocks.as<ZgeBlock>(),
+                                       h->d_plan.as<ZgePlan>(), h->d_groups.as<uint32_t>(), h->d_pblocks.as<ZgeBlock>());
+                    hipLaunchKernelGGL(zarc_zge_entropy_p2_split, dim3((unsigned)nb), dim3(64), 0, h->stream, (uint32_t)nb, slot, h->d_pblocks.as<ZgeBlock>(),
+                                       h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof, h->d_plan.as<ZgePlan>(),
+                                       h->d_enc_err.as<uint32_t>(), h->d_zpieces.as<ZgePiece>());
+                } else
+                    hipLaunchKernelGGL(zarc_zge_entropy_split, dim3((unsigned)nb), dim3(64), 0, h->stream, (uint32_t)nb, slot, h->d_pblocks.as<ZgeBlock>(),
+                                       h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof, h->d_zpieces.as<ZgePiece>());
+            } else if (bp[1] - bp[0] > 1) {
                 // the sub-batch holds frames of several blocks (the largest comes first): the entropy stage runs in two passes around the
                 // table plan, which lets the blocks of a group share their sequence tables (zge_entropy.hip: zarc_zge_plan).  (Pass 2 on
                 // its own is bound by LDS instruction issue -- 18.7 ms where its share of the one-pass kernel was 13.7 -- and neither running
@@ -764,7 +798,7 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
                 hipLaunchKernelGGL(zarc_zge_plan, dim3((unsigned)groups.size()), dim3(64), 0, h->stream, (uint32_t)nb, h->d_blocks.as<ZgeBlock>(), h->d_plan.as<ZgePlan>(),
                                    h->d_groups.as<uint32_t>());
                 hipLaunchKernelGGL(zarc_zge_entropy_p2, dim3((unsigned)nb), dim3(64), 0, h->stream, (uint32_t)nb, slot, h->d_blocks.as<ZgeBlock>(),
-                                   h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof, h->d_plan.as<ZgePlan>());
+                                   h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof, h->d_plan.as<ZgePlan>(), h->d_enc_err.as<uint32_t>());
             } else
                 hipLaunchKernelGGL(zarc_zge_entropy, dim3((unsigned)nb), dim3(64), 0, h->stream, (uint32_t)nb, slot, h->d_blocks.as<ZgeBlock>(),
                                    h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof);
@@ -772,9 +806,14 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
         ZHIP(hipGetLastError());
         ZHIP(t.mark(&c));
         if (!xxh_joined) { ZHIP(hipStreamWaitEvent(h->stream, h->ev_join, 0)); xxh_joined = true; }
-        hipLaunchKernelGGL(zarc_zge_assemble, dim3((unsigned)m), dim3(256), 0, h->stream, P, base, d_off, d_len, h->d_order.as<uint32_t>(), (uint32_t)m,
-                           h->d_block_prefix.as<uint64_t>(), h->d_blocks.as<ZgeBlock>(), h->d_out.as<uint8_t>(), h->d_xxh.as<uint64_t>(),
-                           (uint8_t *)d_dst, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>());
+        if (split)
+            hipLaunchKernelGGL(zarc_zge_assemble_split, dim3((unsigned)m), dim3(256), 0, h->stream, P, base, d_off, d_len, h->d_order.as<uint32_t>(), (uint32_t)m,
+                               h->d_block_prefix.as<uint64_t>(), h->d_blocks.as<ZgeBlock>(), h->d_out.as<uint8_t>(), h->d_xxh.as<uint64_t>(),
+                               (uint8_t *)d_dst, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>(), h->d_pblocks.as<ZgeBlock>(), h->d_zpieces.as<ZgePiece>());
+        else
+            hipLaunchKernelGGL(zarc_zge_assemble, dim3((unsigned)m), dim3(256), 0, h->stream, P, base, d_off, d_len, h->d_order.as<uint32_t>(), (uint32_t)m,
+                               h->d_block_prefix.as<uint64_t>(), h->d_blocks.as<ZgeBlock>(), h->d_out.as<uint8_t>(), h->d_xxh.as<uint64_t>(),
+                               (uint8_t *)d_dst, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>());
         ZHIP(hipGetLastError());
         ZHIP(t.mark(&d));
         HOST_PHASE(3); // launches
@@ -803,7 +842,10 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
     if (!have_digests) ZHIP(hipStreamWaitEvent(h->stream, h->ev_join3, 0)); // the digests are done
     ZHIP(hipMemcpyAsync(dst_len, h->d_dst_len.p, n * 8, hipMemcpyDeviceToHost, h->stream));
     if (!have_digests) ZHIP(hipMemcpyAsync(digest, h->d_digests.p, n * 32, hipMemcpyDeviceToHost, h->stream));
+    uint32_t enc_err = 0;
+    ZHIP(hipMemcpyAsync(&enc_err, h->d_enc_err.p, 4, hipMemcpyDeviceToHost, h->stream));
     ZHIP(hipStreamSynchronize(h->stream));
+    if (enc_err) { set_error(h, "internal: a block the table plan guaranteed to end up compressed did not (its successor may repeat tables the decoder never saw)"); return ZARC_GPU_E_DEVICE; }
     if (status) for (size_t i = 0; i < n; i++) status[i] = ZARC_GPU_FRAME_OK;
     HOST_PHASE(5); // results back
 #ifdef ZARC_GPU_DIAG

@@ -64,6 +64,21 @@ struct ZgePlan {
     ZgePlanTable t[3];   // LL, OF, ML
 };
 static_assert(sizeof(ZgePlanTable) == 476 && sizeof(ZgePlan) == 32 + 3 * 476, "plan record layout");
+// Block splitting (ZARC_GPU_PX_BLOCK_SPLIT, off by default; zge_split.hip, model: tests/support/split_model.c).  A 64 KiB parent block
+// becomes up to ZGE_SPLIT_K pieces = Zstandard blocks, cut at sequence boundaries where the literal statistics change.  Every parent
+// owns ZGE_SPLIT_K piece slots (slot = parent * ZGE_SPLIT_K + k): a ZgeBlock record (type 3 = slot not used; pad of slot 0 = the
+// parent's number of pieces), a ZgePiece that places the piece inside its parent's scratch slots, and a ZgePlan.
+constexpr uint32_t ZGE_SPLIT_K = 16;          // chunks of a parent a cut can fall between, and so its largest number of pieces
+constexpr uint32_t ZGE_SPLIT_PIECE_COST = 192; // bytes the cut rule charges per piece (headers, table descriptions, lost repeat codes)
+constexpr uint32_t ZGE_PIECE_UNUSED = 3;      // ZgeBlock.type of an idle piece slot
+struct ZgePiece {
+    uint32_t seq_first; // first sequence (of the parent's joined ones); the count is the piece record's nseq
+    uint32_t lit_first; // first literal; the count is the piece record's nlit
+    uint32_t src_off;   // first source byte, relative to the parent; the length is the piece record's src_len
+    uint32_t out_off;   // where the coded piece goes inside the parent's output slot ...
+    uint32_t out_cap;   // ... and how many bytes it may take there (src_len + 64: whatever does not fit is a raw block anyway)
+    uint32_t pad[3];
+};
 // one sequence: ofv (28 bits) | ll << 28 (18 bits) | ml << 46 (18 bits)
 __host__ __device__ inline uint64_t zge_pack_seq(uint32_t ll, uint32_t ml, uint32_t ofv) { return (uint64_t)ofv | ((uint64_t)ll << 28) | ((uint64_t)ml << 46); }
 __host__ __device__ inline uint32_t zge_seq_ofv(uint64_t s) { return (uint32_t)(s & 0xFFFFFFFu); }
@@ -199,8 +214,23 @@ __global__ void zarc_zge_entropy(uint32_t n_blocks, uint32_t slot_bytes, ZgeBloc
 __global__ void zarc_zge_entropy_p1(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *blocks, uint64_t *seq_scratch, const uint8_t *lit_scratch,
                                     uint8_t *out_scratch, unsigned long long *prof, ZgePlan *plans);
 __global__ void zarc_zge_plan(uint32_t n_blocks, const ZgeBlock *blocks, ZgePlan *plans, const uint32_t *group_start);
+// (*err |= 1 when a block the plan `guaranteed` to end up compressed did not: its successor may repeat tables the decoder never saw)
 __global__ void zarc_zge_entropy_p2(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *blocks, uint64_t *seq_scratch, const uint8_t *lit_scratch,
-                                    uint8_t *out_scratch, unsigned long long *prof, ZgePlan *plans);
+                                    uint8_t *out_scratch, unsigned long long *prof, ZgePlan *plans, uint32_t *err);
 __global__ void zarc_zge_assemble(ZgeParams P, const uint8_t *src_base, const uint64_t *src_off, const uint64_t *src_len,
                                   const uint32_t *order, uint32_t n_frames, const uint64_t *block_prefix, const ZgeBlock *blocks, const uint8_t *out_scratch,
                                   const uint64_t *xxh, uint8_t *dst_base, const uint64_t *dst_off, uint64_t *dst_len);
+// ---- block splitting on: the cut decision, then the same stages over the parents' pieces (pblocks / plans / pieces: ZGE_SPLIT_K slots per parent)
+__global__ void zarc_zge_split(uint32_t n_blocks, uint32_t slot_bytes, const ZgeBlock *blocks, uint64_t *seq_scratch, const uint8_t *lit_scratch,
+                               ZgeBlock *pblocks, ZgePiece *pieces);
+__global__ void zarc_zge_entropy_split(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *pblocks, uint64_t *seq_scratch, const uint8_t *lit_scratch,
+                                       uint8_t *out_scratch, unsigned long long *prof, const ZgePiece *pieces);
+__global__ void zarc_zge_entropy_p1_split(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *pblocks, uint64_t *seq_scratch, const uint8_t *lit_scratch,
+                                          uint8_t *out_scratch, unsigned long long *prof, ZgePlan *plans, const ZgePiece *pieces);
+__global__ void zarc_zge_plan_split(uint32_t n_blocks, const ZgeBlock *blocks, ZgePlan *plans, const uint32_t *group_start, const ZgeBlock *pblocks);
+__global__ void zarc_zge_entropy_p2_split(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *pblocks, uint64_t *seq_scratch, const uint8_t *lit_scratch,
+                                          uint8_t *out_scratch, unsigned long long *prof, ZgePlan *plans, uint32_t *err, const ZgePiece *pieces);
+__global__ void zarc_zge_assemble_split(ZgeParams P, const uint8_t *src_base, const uint64_t *src_off, const uint64_t *src_len,
+                                        const uint32_t *order, uint32_t n_frames, const uint64_t *block_prefix, const ZgeBlock *blocks, const uint8_t *out_scratch,
+                                        const uint64_t *xxh, uint8_t *dst_base, const uint64_t *dst_off, uint64_t *dst_len, const ZgeBlock *pblocks,
+                                        const ZgePiece *pieces);

@@ -20,12 +20,18 @@ __device__ __forceinline__ void group_copy(uint8_t *__restrict__ d, const uint8_
 
 // One workgroup per frame: block payloads are gathered from the per-block scratch slots (or from the
 // source for raw / RLE blocks) into one contiguous frame.
-__global__ void __launch_bounds__(256) zarc_zge_assemble(ZgeParams P, const uint8_t *__restrict__ src_base, const uint64_t *__restrict__ src_off,
-                                                         const uint64_t *__restrict__ src_len, const uint32_t *__restrict__ order, uint32_t n_frames,
-                                                         const uint64_t *__restrict__ block_prefix,
-                                                         const ZgeBlock *__restrict__ blocks, const uint8_t *__restrict__ out_scratch,
-                                                         const uint64_t *__restrict__ xxh, uint8_t *__restrict__ dst_base,
-                                                         const uint64_t *__restrict__ dst_off, uint64_t *__restrict__ dst_len)
+// SPLIT (ZARC_GPU_PX_BLOCK_SPLIT): every parent block goes out as its pieces, one 3-byte header each, Last_Block on the last piece of
+// the last parent -- unless the pieces with their headers cost more than src_len + 3, what the parent costs as ONE raw block: then it
+// is one (a raw piece costs its bytes, so only headers can push a parent over).  That keeps zarc_gpu_bound() a bound.
+namespace {
+template <bool SPLIT>
+__device__ __forceinline__ void zge_assemble_body(const ZgeParams &P, const uint8_t *__restrict__ src_base, const uint64_t *__restrict__ src_off,
+                                                  const uint64_t *__restrict__ src_len, const uint32_t *__restrict__ order, uint32_t n_frames,
+                                                  const uint64_t *__restrict__ block_prefix,
+                                                  const ZgeBlock *__restrict__ blocks, const uint8_t *__restrict__ out_scratch,
+                                                  const uint64_t *__restrict__ xxh, uint8_t *__restrict__ dst_base,
+                                                  const uint64_t *__restrict__ dst_off, uint64_t *__restrict__ dst_len,
+                                                  const ZgeBlock *__restrict__ pblocks, const ZgePiece *__restrict__ pieces)
 {
     if (blockIdx.x >= n_frames) return;
     const uint32_t f = order[blockIdx.x]; // block_prefix / scratch slots are indexed by position in the sub-batch
@@ -55,7 +61,27 @@ __global__ void __launch_bounds__(256) zarc_zge_assemble(ZgeParams P, const uint
         if (tid == 0) { dst[pos] = 1; dst[pos + 1] = 0; dst[pos + 2] = 0; }
         pos += 3;
     } else {
-        for (uint32_t b = 0; b < nblocks; b++) {
+        for (uint32_t b = 0; SPLIT && b < nblocks; b++) {
+            const ZgeBlock *pr = pblocks + (first + b) * ZGE_SPLIT_K;
+            const ZgePiece *pp = pieces + (first + b) * ZGE_SPLIT_K;
+            const uint32_t np = pr[0].pad, parent_len = blocks[first + b].src_len;
+            const uint8_t *psrc = src + (uint64_t)b * ZARC_BLOCK;
+            uint32_t total = 0;
+            for (uint32_t k = 0; k < np; k++) total += 3 + (pr[k].type == 2 ? pr[k].out_len : (pr[k].type == 1 ? 1u : pr[k].src_len));
+            const bool whole = total > parent_len + 3; // one raw block instead
+            for (uint32_t k = 0; k < (whole ? 1u : np); k++) {
+                const uint32_t type = whole ? 0u : pr[k].type, len = whole ? parent_len : pr[k].src_len;
+                const uint32_t last = (b + 1 == nblocks && (whole || k + 1 == np)) ? 1u : 0u;
+                const uint32_t hdr = last | (type << 1) | ((type == 2 ? pr[k].out_len : len) << 3);
+                if (tid == 0) { dst[pos] = (uint8_t)hdr; dst[pos + 1] = (uint8_t)(hdr >> 8); dst[pos + 2] = (uint8_t)(hdr >> 16); }
+                pos += 3;
+                const uint8_t *from = type == 2 ? out_scratch + (first + b) * zge_out_stride((uint32_t)P.slot_bytes) + pp[k].out_off : psrc + (whole ? 0u : pp[k].src_off);
+                const uint32_t cnt = type == 2 ? pr[k].out_len : (type == 1 ? 1u : len);
+                group_copy(dst + pos, from, cnt, tid, (int)blockDim.x);
+                pos += cnt;
+            }
+        }
+        for (uint32_t b = 0; !SPLIT && b < nblocks; b++) {
             const ZgeBlock rec = blocks[first + b];
             const uint32_t last = b + 1 == nblocks ? 1u : 0u;
             const uint32_t size_field = rec.type == 2 ? rec.out_len : rec.src_len;
@@ -77,6 +103,27 @@ __global__ void __launch_bounds__(256) zarc_zge_assemble(ZgeParams P, const uint
         pos += 4;
     }
     if (tid == 0) dst_len[f] = pos;
+}
+} // namespace
+
+__global__ void __launch_bounds__(256) zarc_zge_assemble(ZgeParams P, const uint8_t *__restrict__ src_base, const uint64_t *__restrict__ src_off,
+                                                         const uint64_t *__restrict__ src_len, const uint32_t *__restrict__ order, uint32_t n_frames,
+                                                         const uint64_t *__restrict__ block_prefix,
+                                                         const ZgeBlock *__restrict__ blocks, const uint8_t *__restrict__ out_scratch,
+                                                         const uint64_t *__restrict__ xxh, uint8_t *__restrict__ dst_base,
+                                                         const uint64_t *__restrict__ dst_off, uint64_t *__restrict__ dst_len)
+{
+    zge_assemble_body<false>(P, src_base, src_off, src_len, order, n_frames, block_prefix, blocks, out_scratch, xxh, dst_base, dst_off, dst_len, nullptr, nullptr);
+}
+__global__ void __launch_bounds__(256) zarc_zge_assemble_split(ZgeParams P, const uint8_t *__restrict__ src_base, const uint64_t *__restrict__ src_off,
+                                                               const uint64_t *__restrict__ src_len, const uint32_t *__restrict__ order, uint32_t n_frames,
+                                                               const uint64_t *__restrict__ block_prefix,
+                                                               const ZgeBlock *__restrict__ blocks, const uint8_t *__restrict__ out_scratch,
+                                                               const uint64_t *__restrict__ xxh, uint8_t *__restrict__ dst_base,
+                                                               const uint64_t *__restrict__ dst_off, uint64_t *__restrict__ dst_len,
+                                                               const ZgeBlock *__restrict__ pblocks, const ZgePiece *__restrict__ pieces)
+{
+    zge_assemble_body<true>(P, src_base, src_off, src_len, order, n_frames, block_prefix, blocks, out_scratch, xxh, dst_base, dst_off, dst_len, pblocks, pieces);
 }
 
 // Dense copy of n scattered byte ranges (frames in their worst-case slots -> back to back), so that the host-pointer

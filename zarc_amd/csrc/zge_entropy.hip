@@ -14,8 +14,12 @@
 //     FSE state chains run on lanes 0..2 with the per-symbol constants fetched by all lanes beforehand (one
 //     dependent LDS access per step), then all 64 lanes pack their sequence's bit fields the same way
 // Bit-identical to oracle/zstd_enc_model.c (encode_literals / encode_sequences).
+// With ZARC_GPU_PX_BLOCK_SPLIT the unit is a PIECE of a block instead (zge_split.hip decides the cuts): the SPLIT instantiations of the
+// three kernels and of the plan run over ZGE_SPLIT_K piece slots per block and code a piece from an offset inside its parent's
+// sequence / literal / output slots, bit-identical to tests/support/split_model.c.  The switch-off kernels are the same code as before.
 #include "zarc_device.h"
 #include "zarc_kernels.h"
+#include "zge_seq_join.h"
 
 namespace {
 
@@ -612,25 +616,33 @@ struct WavePacker {
 // PHASE 0: the whole stage in one pass (every block chooses its sequence tables alone).  PHASE 1 / 2: the same code cut in two where
 // the tables are chosen -- pass 1 ends with the block's code histograms and own choices in plans[bi], zarc_zge_plan settles the tables of
 // each group of blocks, pass 2 builds them and codes the sequences.  Blocks without sequences to code are finished by pass 1.
-template <int PHASE>
+// SPLIT (ZARC_GPU_PX_BLOCK_SPLIT): the wave of a parent block codes the parent's PIECES one after the other, each exactly like a block
+// -- blocks[] / plans[] are the piece slots' records (ZGE_SPLIT_K per parent; `bi` is the slot), and pieces[] says where inside the
+// parent's sequence, literal and output slots the piece lies (zge_split.hip).  Literal positions in seq[] stay the parent's: the first
+// literal length is taken from the piece's first literal.  (A wave per piece SLOT with idle slots leaving at once was measured first:
+// sixteen times the workgroups cost ten times the stage, launching a workgroup being what bounds a grid of idle ones.)
+template <int PHASE, bool SPLIT>
 __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *__restrict__ blocks, uint64_t *__restrict__ seq_scratch,
                                                  const uint8_t *__restrict__ lit_scratch, uint8_t *__restrict__ out_scratch,
-                                                 unsigned long long *__restrict__ prof /* stage ticks (diagnostics) or null */, ZgePlan *__restrict__ plans)
+                                                 unsigned long long *__restrict__ prof /* stage ticks (diagnostics) or null */, ZgePlan *__restrict__ plans,
+                                                 uint32_t *__restrict__ err /* pass 2: the plan guard's error word */, const ZgePiece *__restrict__ pieces,
+                                                 const uint32_t bi)
 {
     const int lane = zd::lane_id();
     unsigned long long tprev = ZGE_CLOCK();
-    const uint32_t bi = blockIdx.x;
     if (bi >= n_blocks) return;
     ZgeBlock *rec = blocks + bi;
     ZgePlan *const plan = PHASE ? plans + bi : nullptr;
     if (PHASE == 2 && !plan->active) return;
-    if (rec->type == 1) { if (PHASE == 1 && lane == 0) plan->active = 0; return; } // RLE block: nothing to code
+    if (rec->type == 1 || (SPLIT && rec->type == ZGE_PIECE_UNUSED)) { if (PHASE == 1 && lane == 0) plan->active = 0; return; } // RLE block (or an idle piece slot): nothing to code
     const uint32_t nlit = rec->nlit, src_len = rec->src_len;
     uint32_t nseq = PHASE == 2 ? plan->nseq : rec->nseq;
-    uint64_t *seq = seq_scratch + (uint64_t)bi * zge_seq_stride(slot_bytes);
-    const uint8_t *lit = lit_scratch + (uint64_t)bi * zge_lit_stride(slot_bytes);
-    uint8_t *out = out_scratch + (uint64_t)bi * zge_out_stride(slot_bytes);
-    const uint32_t out_cap = (uint32_t)zge_out_stride(slot_bytes);
+    const uint32_t slot_i = SPLIT ? bi / ZGE_SPLIT_K : bi; // the parent's scratch slots
+    const uint32_t seq_first = SPLIT ? pieces[bi].seq_first : 0u, lit_first = SPLIT ? pieces[bi].lit_first : 0u;
+    uint64_t *seq = seq_scratch + (uint64_t)slot_i * zge_seq_stride(slot_bytes) + seq_first;
+    const uint8_t *lit = lit_scratch + (uint64_t)slot_i * zge_lit_stride(slot_bytes) + lit_first;
+    uint8_t *out = out_scratch + (uint64_t)slot_i * zge_out_stride(slot_bytes) + (SPLIT ? pieces[bi].out_off : 0u);
+    const uint32_t out_cap = SPLIT ? pieces[bi].out_cap : (uint32_t)zge_out_stride(slot_bytes);
     bool fail = false;
 
     // ================= literals section =================
@@ -791,45 +803,11 @@ __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, u
     // a head's length is a difference of the round's prefix sums; the last head of a round stays pending in scalar registers
     // because its run may go on in the next round.
     if (PHASE != 2 && nseq > 1) {
-        const uint64_t lt = (1ull << lane) - 1;
-        uint32_t out = 0;                       // heads so far, including the pending one
-        uint32_t pend_lp = 0, pend_ml = 0, pend_o = 0, c_lp = 0, c_o = 0; // pending head; literal position / offset of the previous round's last sequence
-        bool have_pend = false;
-        uint64_t s_next = (uint32_t)lane < nseq ? seq[lane] : 0; // every pass over the sequences requests its next round before it works on this one
-        for (uint32_t base = 0; base < nseq; base += 64) {
-            const uint32_t cnt = nseq - base < 64 ? nseq - base : 64;
-            const bool valid = (uint32_t)lane < cnt;
-            const uint64_t s = valid ? s_next : 0;
-            if (base + 64 + (uint32_t)lane < nseq) s_next = seq[base + 64 + (uint32_t)lane]; // (this round stores below base + 64 only)
-            const uint32_t lp = zge_seq_ll(s), ml = valid ? zge_seq_ml(s) : 0u, o = zge_seq_ofv(s);
-            uint32_t plp = zd::shfl_up1(lp), po = zd::shfl_up1(o);
-            if (lane == 0) { plp = c_lp; po = c_o; }
-            const bool cont = valid && (base + (uint32_t)lane) > 0 && lp == plp && o == po;
-            const uint64_t hm = zd::ballot(valid && !cont);
-            const uint32_t psum = zd::wave_scan_incl(ml); // inclusive prefix sums of the match lengths
-            const uint32_t first = hm ? (uint32_t)zd::ctz64(hm) : cnt; // lanes before the first head continue the pending head
-            if (first > 0) pend_ml += zd::readlane(psum, first - 1);
-            if (hm) {
-                if (have_pend && lane == 0) seq[out - 1] = zge_pack_seq(pend_lp, pend_ml, pend_o);
-                const uint32_t nh = (uint32_t)__popcll(hm), last = 63u - (uint32_t)__clzll((long long)hm);
-                // my run ends in front of the next head (or with the round)
-                const uint64_t above = lane == 63 ? 0ull : (hm >> (lane + 1)) << (lane + 1);
-                const uint32_t stop = above ? (uint32_t)zd::ctz64(above) : cnt;  // first lane that is not mine
-                const uint32_t run = zd::shfl(psum, (int)stop - 1) - psum + ml;
-                const uint32_t rank = (uint32_t)__popcll(hm & lt);
-                if (((hm >> lane) & 1) && (uint32_t)lane != last) seq[out + rank] = zge_pack_seq(lp, run, o);
-                pend_lp = zd::readlane(lp, last); pend_ml = zd::readlane(run, last); pend_o = zd::readlane(o, last);
-                have_pend = true;
-                out += nh;
-            }
-            c_lp = zd::readlane(lp, cnt - 1); c_o = zd::readlane(o, cnt - 1);
-        }
-        if (have_pend && lane == 0) seq[out - 1] = zge_pack_seq(pend_lp, pend_ml, pend_o);
-        nseq = out;
+        nseq = zge_join_sequences(seq, nseq, lane);
         zd::wave_sync_global(); // the pass below reads what other lanes wrote here
     }
     if (PHASE != 2) {
-        uint32_t r0 = 0, r1 = 0, r2 = 0, carry = 0; // wave-uniform history / literal position carried between rounds
+        uint32_t r0 = 0, r1 = 0, r2 = 0, carry = lit_first; // wave-uniform history / literal position carried between rounds
         uint64_t s_next = (uint32_t)lane < nseq ? seq[lane] : 0;
         for (uint32_t base = 0; base < nseq; base += 64) {
             const uint32_t cnt = nseq - base < 64 ? nseq - base : 64;
@@ -1101,32 +1079,55 @@ __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, u
         if (csz && csz < src_len) { rec->type = 2; rec->out_len = csz; }
         else { rec->type = 0; rec->out_len = src_len; }
         if (PHASE == 1) plan->active = 0; // no sequences to code (or the literals failed): the block record is final
+        // the plan let a successor repeat this block's tables because it could not end up raw -- and it did (the model's -3)
+        if (PHASE == 2 && plan->guaranteed && !(csz && csz < src_len)) atomicOr(err, 1u);
     }
 }
 
 } // namespace
 
-__global__ void __launch_bounds__(64, 5) zarc_zge_entropy(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *__restrict__ blocks, uint64_t *__restrict__ seq_scratch,
-                                                       const uint8_t *__restrict__ lit_scratch, uint8_t *__restrict__ out_scratch,
-                                                       unsigned long long *__restrict__ prof)
+#define ZGE_ENTROPY_ARGS uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *__restrict__ blocks, uint64_t *__restrict__ seq_scratch,                  \
+                         const uint8_t *__restrict__ lit_scratch, uint8_t *__restrict__ out_scratch, unsigned long long *__restrict__ prof
+__global__ void __launch_bounds__(64, 5) zarc_zge_entropy(ZGE_ENTROPY_ARGS)
 {
     __shared__ EntLds L;
-    zge_entropy_body<0>(L, n_blocks, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, nullptr);
+    zge_entropy_body<0, false>(L, n_blocks, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, nullptr, nullptr, nullptr, blockIdx.x);
 }
-__global__ void __launch_bounds__(64, 5) zarc_zge_entropy_p1(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *__restrict__ blocks, uint64_t *__restrict__ seq_scratch,
-                                                          const uint8_t *__restrict__ lit_scratch, uint8_t *__restrict__ out_scratch,
-                                                          unsigned long long *__restrict__ prof, ZgePlan *__restrict__ plans)
+__global__ void __launch_bounds__(64, 5) zarc_zge_entropy_p1(ZGE_ENTROPY_ARGS, ZgePlan *__restrict__ plans)
 {
     __shared__ EntLds L;
-    zge_entropy_body<1>(L, n_blocks, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, plans);
+    zge_entropy_body<1, false>(L, n_blocks, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, plans, nullptr, nullptr, blockIdx.x);
 }
-__global__ void __launch_bounds__(64, 5) zarc_zge_entropy_p2(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *__restrict__ blocks, uint64_t *__restrict__ seq_scratch,
-                                                          const uint8_t *__restrict__ lit_scratch, uint8_t *__restrict__ out_scratch,
-                                                          unsigned long long *__restrict__ prof, ZgePlan *__restrict__ plans)
+__global__ void __launch_bounds__(64, 5) zarc_zge_entropy_p2(ZGE_ENTROPY_ARGS, ZgePlan *__restrict__ plans, uint32_t *__restrict__ err)
 {
     __shared__ EntLds L;
-    zge_entropy_body<2>(L, n_blocks, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, plans);
+    zge_entropy_body<2, false>(L, n_blocks, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, plans, err, nullptr, blockIdx.x);
 }
+// block splitting on: n_blocks parents, a wave each; blocks[] / plans[] / pieces[] hold ZGE_SPLIT_K piece slots per parent, of which the
+// first blocks[parent * ZGE_SPLIT_K].pad are in use.  (The rendezvous separates one piece's LDS traffic from the next one's.)
+#define ZGE_SPLIT_LOOP if (blockIdx.x >= n_blocks) return;                                                                                     \
+    const uint32_t np = blocks[(uint64_t)blockIdx.x * ZGE_SPLIT_K].pad;                                                                        \
+    for (uint32_t k = 0; k < np; k++, zd::wave_sync())
+__global__ void __launch_bounds__(64, 5) zarc_zge_entropy_split(ZGE_ENTROPY_ARGS, const ZgePiece *__restrict__ pieces)
+{
+    __shared__ EntLds L;
+    ZGE_SPLIT_LOOP zge_entropy_body<0, true>(L, n_blocks * ZGE_SPLIT_K, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, nullptr, nullptr, pieces, blockIdx.x * ZGE_SPLIT_K + k);
+}
+__global__ void __launch_bounds__(64, 5) zarc_zge_entropy_p1_split(ZGE_ENTROPY_ARGS, ZgePlan *__restrict__ plans, const ZgePiece *__restrict__ pieces)
+{
+    __shared__ EntLds L;
+    ZGE_SPLIT_LOOP zge_entropy_body<1, true>(L, n_blocks * ZGE_SPLIT_K, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, plans, nullptr, pieces, blockIdx.x * ZGE_SPLIT_K + k);
+    const uint32_t idle = (uint32_t)zd::lane_id(); // the plan walks every slot: the idle ones take no part
+    if (idle >= np && idle < ZGE_SPLIT_K) plans[(uint64_t)blockIdx.x * ZGE_SPLIT_K + idle].active = 0;
+}
+__global__ void __launch_bounds__(64, 5) zarc_zge_entropy_p2_split(ZGE_ENTROPY_ARGS, ZgePlan *__restrict__ plans, uint32_t *__restrict__ err,
+                                                                   const ZgePiece *__restrict__ pieces)
+{
+    __shared__ EntLds L;
+    ZGE_SPLIT_LOOP zge_entropy_body<2, true>(L, n_blocks * ZGE_SPLIT_K, slot_bytes, blocks, seq_scratch, lit_scratch, out_scratch, prof, plans, err, pieces, blockIdx.x * ZGE_SPLIT_K + k);
+}
+#undef ZGE_ENTROPY_ARGS
+#undef ZGE_SPLIT_LOOP
 
 // The table plan (model: zstd_enc_model.c, seq_plan_group).  One wave per group of ZGE_TABLE_GROUP blocks of a frame (the host lists
 // the groups' first block slots), one lane per symbol.  Per table type: the sum of the blocks' histograms is
@@ -1136,12 +1137,17 @@ __global__ void __launch_bounds__(64, 5) zarc_zge_entropy_p2(uint32_t n_blocks, 
 // raw size, i.e. it cannot end up a raw block, whose tables the decoder never sees; the block behind any other describes the table
 // again.  Blocks that keep RLE mode for a type break that type's chain the same way.  Costs fit 32 bits: a group holds at most
 // 16 x 21 845 sequences at 9 x 256 units each.
-__global__ void __launch_bounds__(64) zarc_zge_plan(uint32_t n_blocks, const ZgeBlock *__restrict__ blocks, ZgePlan *__restrict__ plans,
-                                                    const uint32_t *__restrict__ group_start /* first block slot of each group of a multi-block frame */)
+// SPLIT: the group's parents are found the same way (blocks[] = the parent records, `index % ZGE_TABLE_GROUP` is the parent's), and
+// the walk goes over their ZGE_SPLIT_K piece slots each, in frame order; idle slots are inactive.  The pieces of a group hold the
+// parents' sequences between them, so the sums above keep their bounds (256 pieces x 3 descriptions of 80 bytes add 2^27 units at
+// most).  One more rule: a cut parent whose pieces cost more than one raw block goes out as ONE raw block (zge_assemble.hip), and
+// then none of its pieces reaches the decoder -- so behind a cut parent the decoder is known to hold the group's table only if it
+// held it in front of that parent AND holds it behind the parent's last piece (model: split_model.c, split_plan_group).
+namespace {
+template <bool SPLIT>
+__device__ __forceinline__ void zge_plan_body(int16_t (*gnorm)[64], uint8_t (*gdesc)[80], uint32_t *gdl, uint32_t n_blocks, const ZgeBlock *__restrict__ blocks,
+                                              ZgePlan *__restrict__ plans, const uint32_t *__restrict__ group_start, const ZgeBlock *__restrict__ pblocks)
 {
-    __shared__ int16_t gnorm[3][64];
-    __shared__ uint8_t gdesc[3][80];
-    __shared__ uint32_t gdl[3];
     const int lane = zd::lane_id();
     const uint32_t bi = group_start[blockIdx.x];
     if (bi >= n_blocks) return;
@@ -1149,7 +1155,10 @@ __global__ void __launch_bounds__(64) zarc_zge_plan(uint32_t n_blocks, const Zge
     if (index0 % ZGE_TABLE_GROUP) return;
     uint32_t nb = 1;
     while (nb < ZGE_TABLE_GROUP && bi + nb < n_blocks && blocks[bi + nb].frame == frame && blocks[bi + nb].index == index0 + nb) nb++;
-    if (nb < 2) return; // a block on its own keeps its own choices
+    if (!SPLIT && nb < 2) return; // a block on its own keeps its own choices
+    const ZgeBlock *const recs = SPLIT ? pblocks + (uint64_t)bi * ZGE_SPLIT_K : blocks + bi; // the records the walk goes over ...
+    plans += SPLIT ? (uint64_t)bi * ZGE_SPLIT_K : (uint64_t)bi;                               // ... their plans ...
+    if (SPLIT) nb *= ZGE_SPLIT_K;                                                             // ... and how many
     bool use_group[3] = {false, false, false};
     uint32_t g_al[3] = {0, 0, 0}, g_nsym[3] = {0, 0, 0};
 #pragma unroll
@@ -1157,7 +1166,7 @@ __global__ void __launch_bounds__(64) zarc_zge_plan(uint32_t n_blocks, const Zge
         const int max_al = t == 1 ? 8 : 9;
         uint32_t sum = 0, total = 0, cost_own = 0, np = 0;
         for (uint32_t b = 0; b < nb; b++) {
-            const ZgePlan *p = plans + bi + b;
+            const ZgePlan *p = plans + b;
             if (!p->active || p->t[t].mode == 1) continue; // uniform
             sum += p->t[t].count[lane];
             total += p->nseq; cost_own += p->t[t].cost; np++;
@@ -1203,8 +1212,14 @@ __global__ void __launch_bounds__(64) zarc_zge_plan(uint32_t n_blocks, const Zge
     }
     if (!use_group[0] && !use_group[1] && !use_group[2]) return; // every block keeps its own choices: nothing to write
     bool have[3] = {false, false, false}; // the decoder is known to hold the group's table of this type
+    bool entry[3] = {false, false, false}, prev_cut = false; // SPLIT: `have` in front of the current parent; the parent before it was cut
     for (uint32_t b = 0; b < nb; b++) {
-        ZgePlan *p = plans + bi + b;
+        ZgePlan *p = plans + b;
+        if (SPLIT && b % ZGE_SPLIT_K == 0) { // a parent's first slot (its pad = the parent's number of pieces)
+#pragma unroll
+            for (int t = 0; t < 3; t++) { if (prev_cut) have[t] = have[t] && entry[t]; entry[t] = have[t]; }
+            prev_cut = recs[b].pad > 1;
+        }
         if (!p->active) continue; // uniform
         uint32_t ub_bits = 1 + p->extra_bits, hdrs = 0;
         bool grp[3];
@@ -1229,9 +1244,30 @@ __global__ void __launch_bounds__(64) zarc_zge_plan(uint32_t n_blocks, const Zge
         }
         const uint32_t nseq = p->nseq;
         const uint32_t ub = p->lsz + (nseq < 128 ? 1u : (nseq < 0x7F00 ? 2u : 3u)) + 1 + (ub_bits + 7) / 8 + hdrs;
-        const bool guaranteed = ub < blocks[bi + b].src_len;
+        const bool guaranteed = ub < recs[b].src_len;
         if (lane == 0) p->guaranteed = guaranteed ? 1u : 0u;
 #pragma unroll
         for (int t = 0; t < 3; t++) have[t] = grp[t] && guaranteed;
     }
 }
+} // namespace
+
+__global__ void __launch_bounds__(64) zarc_zge_plan(uint32_t n_blocks, const ZgeBlock *__restrict__ blocks, ZgePlan *__restrict__ plans,
+                                                    const uint32_t *__restrict__ group_start /* first block slot of each group of a multi-block frame */)
+{
+    __shared__ int16_t gnorm[3][64];
+    __shared__ uint8_t gdesc[3][80];
+    __shared__ uint32_t gdl[3];
+    zge_plan_body<false>(gnorm, gdesc, gdl, n_blocks, blocks, plans, group_start, nullptr);
+}
+__global__ void __launch_bounds__(64) zarc_zge_plan_split(uint32_t n_blocks, const ZgeBlock *__restrict__ blocks, ZgePlan *__restrict__ plans,
+                                                          const uint32_t *__restrict__ group_start, const ZgeBlock *__restrict__ pblocks)
+{
+    __shared__ int16_t gnorm[3][64];
+    __shared__ uint8_t gdesc[3][80];
+    __shared__ uint32_t gdl[3];
+    zge_plan_body<true>(gnorm, gdesc, gdl, n_blocks, blocks, plans, group_start, pblocks);
+}
+
+// the cut decision of ZARC_GPU_PX_BLOCK_SPLIT (zarc_zge_split): same translation unit, see the note at its top
+#include "zge_split.hip"

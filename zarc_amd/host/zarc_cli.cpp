@@ -180,7 +180,8 @@ bool safe_name(const std::vector<std::string> &name)
 int usage()
 {
     std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|list-files> ...\n"
-                         "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] PATH...\n"
+                         "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] [--split-blocks] PATH...\n"
+                         "         --split-blocks  cut 64 KiB blocks where their statistics change (smaller frames on binaries / JSON; off by default)\n"
                          "       zarc unpack INPUT [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
@@ -316,7 +317,7 @@ int cmd_pack(const std::vector<std::string> &a)
     std::string output;
     std::vector<std::string> paths;
     std::vector<ZstdParam> params;
-    bool store = false, follow = false, have_level = false;
+    bool store = false, follow = false, have_level = false, split_blocks = false;
     int level = 0, gpus = 1;
     for (size_t i = 0; i < a.size(); i++) {
         if (a[i] == "--output" && i + 1 < a.size()) output = a[++i];
@@ -326,6 +327,7 @@ int cmd_pack(const std::vector<std::string> &a)
         else if (a[i] == "--store") store = true;
         else if (a[i] == "-L" || a[i] == "--follow-symlinks") follow = true;
         else if (a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str()); // engine extension: deal every batch to N devices
+        else if (a[i] == "--split-blocks") split_blocks = true;                          // engine extension: ZARC_GPU_PX_BLOCK_SPLIT
         else if (!a[i].empty() && a[i][0] == '-') return usage();
         else paths.push_back(a[i]);
     }
@@ -351,10 +353,11 @@ int cmd_pack(const std::vector<std::string> &a)
             LOGF(1, "advisory zstd parameter", "id=%d value=%d", p.id, p.value);
         }
     if (store) enc.enable_compression(false);
+    if (split_blocks) enc.split_blocks(true);
 
     std::vector<Walked> entries;
     for (const auto &p : paths) walk(p, follow, entries);
-    LOGF(2, "walked", "entries=%zu devices=%d", entries.size(), gpus);
+    LOGF(2, "walked", "entries=%zu devices=%d split_blocks=%d", entries.size(), gpus, split_blocks ? 1 : 0);
     // Contents go to the engine in batches of about 1 GiB.  A reader thread fills batch k+1 (file reads) while this thread has the
     // engine pack batch k and appends its frames to the archive; entries are added in walk order once their digest is known.
     struct Batch { size_t first = 0, last = 0; std::vector<std::vector<uint8_t>> contents; std::vector<size_t> owner; std::string error; };

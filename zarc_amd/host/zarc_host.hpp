@@ -142,6 +142,9 @@ class Encoder {
     void set_zstd_parameter(int id, int value) { for (auto &e : engines_) e->check(zarc_gpu_set_parameter(e->get(), id, value)); }
     // Encoder::enable_compression (encode.rs:95-97)
     void enable_compression(bool compress) { for (auto &e : engines_) zarc_gpu_enable_compression(e->get(), compress ? 1 : 0); }
+    // Engine extension (`zarc pack --split-blocks`): 64 KiB blocks are cut where their literal statistics change
+    // (ZARC_GPU_PX_BLOCK_SPLIT).  Set on every handle, so several devices write the archive one would.
+    void split_blocks(bool on) { set_zstd_parameter(ZARC_GPU_PX_BLOCK_SPLIT, on ? 1 : 0); }
 
     // Encoder::add_data_frame for one entry (content_frame.rs:20)
     Digest add_data_frame(const uint8_t *content, size_t len)
