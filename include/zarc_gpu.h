@@ -10,6 +10,8 @@
  *   unpack : Decoder::read_content_frame        crates/zarc/src/decode/frame_iterator.rs:14-27
  *            FrameIterator::{next,digest,verify} crates/zarc/src/decode/frame_iterator.rs:38-104
  *            ZstdFrameIterator::decompress_step crates/zarc/src/decode/zstd_iterator.rs:88-153
+ *   verify : FrameIterator::verify for a batch, without the bytes   crates/zarc/src/decode/frame_iterator.rs:83-88 (and what
+ *            `zarc unpack` does with its answer, crates/zarc-cli/src/unpack.rs:118-120)
  *   digest : DigestType::verify_data            crates/zarc/src/integrity.rs:107-117
  *   ctx    : CCtx::try_create / init(0) / set_parameter / reset     crates/zarc/src/encode.rs:58-97
  *            DCtx::try_create                   crates/zarc/src/decode/zstd_iterator.rs:29
@@ -34,7 +36,10 @@
 extern "C" {
 #endif
 
-#define ZARC_GPU_ABI_VERSION 2 /* 2: round 3's entry points (device_count, *_dedup, FRAME_DUPLICATE, PX_ZERO_COPY) + round 4's (warnings, levels) */
+#define ZARC_GPU_ABI_VERSION 2 /* 2: round 3's entry points (device_count, *_dedup, FRAME_DUPLICATE, PX_ZERO_COPY) + round 4's (warnings, levels).
+                                  zarc_gpu_verify_batch*, zarc_gpu_last_copy_bytes, ZARC_GPU_PX_CHECK_FRAMES and ZARC_GPU_E_CHECK were added WITHOUT a new
+                                  version (they are new symbols and new ids; nothing older changed): a library from before them fails a caller
+                                  that wants them at the symbol lookup, not by version */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -48,7 +53,8 @@ enum {
     ZARC_GPU_E_NOMEM = -2,       /* "failed allocating zstd context" analogue (encode.rs:61)        */
     ZARC_GPU_E_PARAM = -3,       /* bad argument / parameter out of bounds                          */
     ZARC_GPU_E_UNSUPPORTED = -4, /* parameter accepted by libzstd but not by this engine            */
-    ZARC_GPU_E_DSTSIZE = -5      /* dst_cap smaller than the sum of zarc_gpu_bound() of the entries */
+    ZARC_GPU_E_DSTSIZE = -5,     /* dst_cap smaller than the sum of zarc_gpu_bound() of the entries */
+    ZARC_GPU_E_CHECK = -6        /* pack with ZARC_GPU_PX_CHECK_FRAMES: a frame failed its read-back check; the batch's output is void */
 };
 
 /* per-frame status values (status[i]); names follow ZSTD_getErrorName where one exists */
@@ -99,11 +105,14 @@ enum {
                                         host memcpy pass is skipped.  Default 4096 (a DMA per small scattered buffer is slower than the ring); 0 = always stage.
                                         Ordinary (pageable) buffers are staged either way. */
     /* UNLIKE THE IDS ABOVE THIS ONE CHANGES THE BYTES THAT COME OUT (every frame stays valid Zstandard of the same content). */
-    ZARC_GPU_PX_BLOCK_SPLIT = 9007   /* 0 (default): a block every 64 KiB and nowhere else.  1: a 64 KiB block is cut into up to 16 Zstandard blocks at sequence
+    ZARC_GPU_PX_BLOCK_SPLIT = 9007,  /* 0 (default): a block every 64 KiB and nowhere else.  1: a 64 KiB block is cut into up to 16 Zstandard blocks at sequence
                                         boundaries where its literal statistics change, each with its own Huffman table and table modes (what libzstd 1.5 does
                                         inside compress2).  Smaller frames on ELF / machine code / JSON, the same on text; zarc_gpu_bound() holds unchanged (a
                                         block whose pieces would cost more than one raw block goes out as one).  Store mode ignores it.  Other values:
                                         ZARC_GPU_E_PARAM. */
+    /* ... and this one changes no byte again, only the time a pack call takes */
+    ZARC_GPU_PX_CHECK_FRAMES = 9008  /* 0 (default) / 1; other values ZARC_GPU_E_PARAM.  1: every pack call decodes its own frames again and compares them
+                                        with the sources before it returns ("read-back check" below) */
 };
 /* What the engine does with the libzstd ids (pack.rs:86-217 forwards them all):
  *   CompressionLevel  -131072..22 accepted; four finders (zarc_gpu_level_finder says which one a level runs):
@@ -199,11 +208,21 @@ int zarc_gpu_pack_batch_device_dedup(zarc_gpu_t *h, size_t n, const void *d_src_
                                      uint64_t *dst_len, uint8_t *digest /* n*32 */, int *status,
                                      zarc_gpu_known_fn known, void *ctx);
 
+/* Read-back check (ZARC_GPU_PX_CHECK_FRAMES = 1; sticky; all four pack entry points).  Before a pack call returns, while sources and
+ * assembled frames are still in HBM, the engine's own decoder decodes every frame of the call (compressed, split-block and store-mode
+ * alike; ZARC_GPU_FRAME_DUPLICATE entries have no frame) into scratch of the handle and the decoded bytes are compared with the source
+ * bytes, exactly; with the checksum flag the frame's four trailer bytes are compared with the XXH64 of the source as well.  The digest
+ * needs no second look: it was computed from the source, and the source was just compared.  Any bad entry: status[i] =
+ * ZARC_GPU_FRAME_CORRUPT where status was given, dst_len[i] = 0, zarc_gpu_last_error() names the first bad index of the batch and its
+ * first differing byte (or the checksum trailer), and the call returns ZARC_GPU_E_CHECK: treat the batch's output as void.  The
+ * decode scratch counts against ZARC_GPU_PX_SCRATCH_MB like verify's.  With the switch off none of this runs and nothing is reserved. */
+
 /* ---- unpack: Zstandard frame decode (+ XXH64 verify) + BLAKE3 verify --------------------------- */
 /* frame[i]/frame_len[i] = Frame.offset/.length slice of the archive, raw_len[i] = Frame.uncompressed
  * (crates/zarc/src/directory/frame.rs:17-31), dst[i] = buffer of raw_len[i] bytes.  expect may be NULL;
  * when given, a mismatch sets status[i] = ZARC_GPU_FRAME_DIGEST but the bytes are still delivered
- * (unpack.rs:118-120).  digest[i] always receives the BLAKE3 of what was decoded. */
+ * (unpack.rs:118-120).  digest[i] always receives the BLAKE3 of what was decoded; a frame that did not decode
+ * (any other status than OK / CHECKSUM / DIGEST) has no content and gets an all-zero digest. */
 int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len,
                           const size_t *raw_len, void *const *dst,
                           const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN],
@@ -212,6 +231,20 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 int zarc_gpu_unpack_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off,
                                  const uint64_t *frame_len, void *d_dst_base, const uint64_t *dst_off,
                                  const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */,
+                                 uint8_t *digest /* n*32 */, int *status);
+
+/* ---- verify: FrameIterator::verify() for a batch, without the bytes ----------------------------- */
+/* What FrameIterator::verify() (crates/zarc/src/decode/frame_iterator.rs:83-88) answers once a frame has been read to its end, and what
+ * `zstd --test` does for one file: is this frame good?  Arguments and results as zarc_gpu_unpack_batch minus dst: status[i] and
+ * digest[i] are EXACTLY what unpack gives for the same frame (the same decoder, XXH64 / BLAKE3 passes and verdict run; a digest
+ * mismatch is ZARC_GPU_FRAME_DIGEST, reported and not fatal, unpack.rs:118-120).  The decoded bytes go to scratch the handle owns
+ * and never to the caller: the host form moves only the compressed bytes host-to-device and nothing back but 36 bytes per frame.
+ * The scratch counts against ZARC_GPU_PX_SCRATCH_MB: a batch whose decoded bytes (plus decoder scratch) exceed it is verified in
+ * parts; a single frame larger than the budget runs alone. */
+int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                          const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status);
+int zarc_gpu_verify_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off,
+                                 const uint64_t *frame_len, const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */,
                                  uint8_t *digest /* n*32 */, int *status);
 
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
@@ -241,6 +274,11 @@ enum {
     ZARC_GPU_T_COUNT = 10
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);
+/* Content bytes the most recent batch call moved between host and device (descriptor arrays, statuses, digests not counted).  Every
+ * batch call sets them; the device-memory forms report 0.  H2D + D2H == RING + DIRECT. */
+enum { ZARC_GPU_C_H2D = 0, ZARC_GPU_C_D2H = 1, ZARC_GPU_C_RING = 2 /* of those, through the pinned staging ring */,
+       ZARC_GPU_C_DIRECT = 3 /* of those, DMA straight from/to the caller's page-locked memory */, ZARC_GPU_C_COUNT = 4 };
+uint64_t zarc_gpu_last_copy_bytes(const zarc_gpu_t *h, int which);
 /* Fill a device buffer with entries of the synthetic corpus; entry i of the
  * call is corpus entry first_index+i, kind = index mod 4 when kind < 0. */
 int zarc_gpu_corpus_fill_device(zarc_gpu_t *h, size_t n, void *d_base, const uint64_t *off,

@@ -16,7 +16,7 @@ ALIGN = 16
 PAD = 64
 
 # call-level errors
-OK, E_DEVICE, E_NOMEM, E_PARAM, E_UNSUPPORTED, E_DSTSIZE = 0, -1, -2, -3, -4, -5
+OK, E_DEVICE, E_NOMEM, E_PARAM, E_UNSUPPORTED, E_DSTSIZE, E_CHECK = 0, -1, -2, -3, -4, -5, -6
 # per-frame status
 FRAME_OK, FRAME_CORRUPT, FRAME_CHECKSUM, FRAME_DIGEST, FRAME_DSTSIZE, FRAME_BAD_MAGIC, FRAME_UNSUPPORTED, FRAME_SRCSIZE, FRAME_DUPLICATE = range(9)
 # parameter ids (ZSTD_cParameter values, what zstd_safe::CParameter maps to)
@@ -27,6 +27,10 @@ P_CONTENT_SIZE_FLAG, P_CHECKSUM_FLAG, P_DICT_ID_FLAG = 200, 201, 202
 PX_SCRATCH_MB, PX_STAGE_CHUNK, PX_STAGE_THREAD, PX_COPY_THREADS, PX_DEC_GROUPS, PX_ZERO_COPY = 9001, 9002, 9003, 9004, 9005, 9006
 # ... and the one engine switch that DOES change the frames: 1 = 64 KiB blocks are cut where their literal statistics change (default 0)
 PX_BLOCK_SPLIT = 9007
+# read-back check of pack: 1 = every frame of a pack call is decoded again and compared with its source before the call returns (default 0)
+PX_CHECK_FRAMES = 9008
+# zarc_gpu_last_copy_bytes: content bytes the most recent batch call moved over PCIe
+C_H2D, C_D2H, C_RING, C_DIRECT = range(4)
 # timers
 T_BLAKE3, T_XXH64, T_MATCH, T_ENTROPY, T_ASSEMBLE, T_DECODE, T_TOTAL, T_DEC_SEQS, T_DEC_LITS, T_DEC_FRAMES = range(10)
 
@@ -34,6 +38,7 @@ EXPORTS = [
     "zarc_gpu_abi_version", "zarc_gpu_level_finder", "zarc_gpu_parameter_advisory", "zarc_gpu_device_count", "zarc_gpu_create", "zarc_gpu_destroy", "zarc_gpu_set_parameter", "zarc_gpu_get_params",
     "zarc_gpu_enable_compression", "zarc_gpu_bound", "zarc_gpu_error_name", "zarc_gpu_frame_status_name", "zarc_gpu_last_error",
     "zarc_gpu_pack_batch", "zarc_gpu_pack_batch_device", "zarc_gpu_pack_batch_dedup", "zarc_gpu_pack_batch_device_dedup", "zarc_gpu_unpack_batch", "zarc_gpu_unpack_batch_device",
+    "zarc_gpu_verify_batch", "zarc_gpu_verify_batch_device", "zarc_gpu_last_copy_bytes",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -92,6 +97,10 @@ def load(path=None):
     lib.zarc_gpu_pack_batch_device_dedup.argtypes = [vp, sz, vp, u64p, u64p, vp, sz, u64p, u64p, vp, ip, KNOWN_FN, vp]
     lib.zarc_gpu_unpack_batch.argtypes = [vp, sz, vpp, szp, szp, vpp, vp, vp, ip]
     lib.zarc_gpu_unpack_batch_device.argtypes = [vp, sz, vp, u64p, u64p, vp, u64p, u64p, vp, vp, ip]
+    lib.zarc_gpu_verify_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vp, ip]
+    lib.zarc_gpu_verify_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, ip]
+    lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
+    lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]
     lib.zarc_gpu_blake3_batch_device.argtypes = [vp, sz, vp, u64p, u64p, vp]
     lib.zarc_gpu_xxh64_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p]

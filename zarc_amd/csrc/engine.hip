@@ -9,7 +9,9 @@
 #include "../../include/zarc_gpu.h"
 #include "zarc_kernels.h"
 #include <algorithm>
+#include <atomic>
 #include <chrono>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -99,6 +101,17 @@ struct zarc_gpu {
     uint8_t *meta_pin = nullptr; // page-locked arena for descriptor uploads (meta_take)
     size_t meta_cap = 0, meta_used = 0;
     int ldm[5] = {0, 0, 0, 0, 0}; // EnableLongDistanceMatching, LdmHashLog, LdmMinMatch, LdmBucketSizeLog, LdmHashRateLog: remembered, advisory
+    // verify (zarc_gpu_verify_batch*) and the read-back check of pack (ZARC_GPU_PX_CHECK_FRAMES): the decoder writes into scratch the handle owns
+    DevBuf d_vout;              // decoded bytes, 16-byte aligned offsets; counts against scratch_budget
+    DevBuf d_chk_off;           // read-back check: the decoder's output offsets (pack keeps d_dst_off for its later sub-batches)
+    DevBuf d_chk_order, d_chk_slices, d_chk_bad; // zarc_check_compare: entry of every sorted frame, slice prefix, first differing byte
+    int check_frames = 0;       // ZARC_GPU_PX_CHECK_FRAMES
+    size_t chk_index = 0;       // the first entry that failed the check in the most recent pack pass, and where (ZARC_CHECK_TRAILER: its trailer)
+    uint32_t chk_at = 0;
+    float chk_ms = 0;           // zarc_check_compare of the most recent pack pass (diagnostic build prints it)
+    // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
+    std::atomic<uint64_t> copy_bytes[ZARC_GPU_C_COUNT] = {};
+    bool nested = false;        // a host-pointer entry point is running: the device forms it calls leave the counters alone
     int zero_copy = 4096;      // ZARC_GPU_PX_ZERO_COPY: page-locked caller memory in runs of this many KiB on average is read / written by the DMA engines directly (0 = never)
 };
 
@@ -231,7 +244,7 @@ inline uint64_t blocks_of(uint64_t len) { return len == 0 ? 1 : (len + ZARC_BLOC
 
 struct Timer {
     zarc_gpu *h;
-    int next = 0;
+    int next = 0; // (the read-back check of pack starts at 8: pack's own marks stay valid)
     hipError_t mark(int *idx) { *idx = next; return hipEventRecord(h->ev[next++], h->stream); }
 };
 
@@ -328,8 +341,16 @@ int check_common(zarc_gpu *h, size_t n)
     ZHIP(hipSetDevice(h->device));
     for (int i = 0; i < ZARC_GPU_T_COUNT; i++) h->ms[i] = -1.f;
     h->meta_used = 0; // every batch call ends with its stream synchronised: what the arena held has been copied
+    if (!h->nested) for (auto &c : h->copy_bytes) c.store(0, std::memory_order_relaxed);
     return 0;
 }
+
+// the host-pointer entry points call the device forms per chunk: those must not reset what the call has counted so far
+struct NestedCall {
+    zarc_gpu *h;
+    explicit NestedCall(zarc_gpu *h_) : h(h_) { h->nested = true; }
+    ~NestedCall() { h->nested = false; }
+};
 
 } // namespace
 
@@ -401,6 +422,7 @@ void zarc_gpu_destroy(zarc_gpu_t *h)
     if (h->ev_join3) (void)hipEventDestroy(h->ev_join3);
     for (int i = 0; i < zarc_gpu::PIN_SLOTS; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     h->d_dense.release(); h->d_goff.release(); h->d_glen.release(); h->d_gdense.release();
+    h->d_vout.release(); h->d_chk_off.release(); h->d_chk_order.release(); h->d_chk_slices.release(); h->d_chk_bad.release();
     if (h->meta_pin) (void)hipHostFree(h->meta_pin);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -443,6 +465,7 @@ int zarc_gpu_set_parameter(zarc_gpu_t *h, int id, int value)
         h->dec_groups = value; return ZARC_GPU_OK;
     case ZARC_GPU_PX_ZERO_COPY: if (value < 0 || value > (1 << 20)) return ZARC_GPU_E_PARAM; h->zero_copy = value; return ZARC_GPU_OK;
     case ZARC_GPU_PX_BLOCK_SPLIT: if (value != 0 && value != 1) return ZARC_GPU_E_PARAM; h->block_split = value; return ZARC_GPU_OK;
+    case ZARC_GPU_PX_CHECK_FRAMES: if (value != 0 && value != 1) return ZARC_GPU_E_PARAM; h->check_frames = value; return ZARC_GPU_OK;
     case ZARC_GPU_P_CONTENT_SIZE_FLAG:
         if (value != 1) return ZARC_GPU_E_UNSUPPORTED; // frames always carry their content size
         return ZARC_GPU_OK;
@@ -497,6 +520,7 @@ const char *zarc_gpu_error_name(int code)
     case ZARC_GPU_E_PARAM: return "Parameter is out of bound";
     case ZARC_GPU_E_UNSUPPORTED: return "Unsupported parameter";
     case ZARC_GPU_E_DSTSIZE: return "Destination buffer is too small";
+    case ZARC_GPU_E_CHECK: return "Frame failed its read-back check";
     default: return "Unspecified error code";
     }
 }
@@ -516,6 +540,7 @@ const char *zarc_gpu_frame_status_name(int s)
     }
 }
 const char *zarc_gpu_last_error(const zarc_gpu_t *h) { return h ? h->last_error.c_str() : "null handle"; }
+uint64_t zarc_gpu_last_copy_bytes(const zarc_gpu_t *h, int which) { return (h && which >= 0 && which < ZARC_GPU_C_COUNT) ? h->copy_bytes[which].load(std::memory_order_relaxed) : 0; }
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which) { return (h && which >= 0 && which < ZARC_GPU_T_COUNT) ? h->ms[which] : -1.f; }
 
 // ---------------------------------------------------------------------------------------------------
@@ -561,6 +586,24 @@ int zarc_gpu_xxh64_batch_device(zarc_gpu_t *h, size_t n, const void *d_base, con
 
 } // extern "C"
 namespace {
+// Read-back check of a pack pass (ZARC_GPU_PX_CHECK_FRAMES): the decoder runs DECODE-ONLY -- no hash passes, no verdict, nothing written to
+// h->ms -- and zarc_check_compare takes their place.  Pack's own buffers stay as they are: the decoder leaves d_off / d_len / d_dst_len /
+// d_xxh / d_digests alone in this mode, puts its output offsets into d_chk_off instead of d_dst_off, and takes its timing events from
+// the upper half of the pool (pack's e0 .. e2 and the sub-batch marks live in the lower one).
+struct PackCheck {
+    const uint8_t *src_base;   // the pack pass's sources (offsets / lengths: h->d_off, h->d_len, by entry)
+    bool trailer;              // frames carry the checksum trailer: compare it with h->d_xxh
+    uint32_t entry0;           // the decoder's frame 0 is this entry of the pack pass (parts of a split batch)
+    uint32_t *first_bad;       // host, by entry from entry0 on: ZARC_CHECK_CLEAN, a byte offset, or ZARC_CHECK_TRAILER
+    float *ms;                 // += device time of zarc_check_compare
+};
+
+int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, void *d_dst_base,
+                        const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk);
+int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, uint64_t *dst_len,
+               int *status, bool trailer);
+void check_message(zarc_gpu_t *h, size_t index);
+
 // have_digests: the caller has hashed the entries already (hash-first dedup): no digest kernels, `digest` is not written
 int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
                      size_t dst_cap, uint64_t *dst_off, uint64_t *dst_len, uint8_t *digest, int *status, bool have_digests)
@@ -636,6 +679,7 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
         h->ms[ZARC_GPU_T_ENTROPY] = 0;
         h->ms[ZARC_GPU_T_ASSEMBLE] = elapsed(h, e1, e2);
         h->ms[ZARC_GPU_T_TOTAL] = h->ms[ZARC_GPU_T_BLAKE3] + h->ms[ZARC_GPU_T_ASSEMBLE];
+        if (h->check_frames) return check_pack(h, n, d_src_base, src_len, d_dst, dst_off, dst_len, status, /*trailer=*/false);
         return ZARC_GPU_OK;
     }
     ZHIP(t.mark(&e2));
@@ -858,7 +902,56 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
     h->ms[ZARC_GPU_T_ENTROPY] = ms_ent;
     h->ms[ZARC_GPU_T_ASSEMBLE] = ms_asm;
     h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e1) + ms_match + ms_ent + ms_asm; // the digest and the checksum run beside these
+    // read-back check: pack has taken its results off the buffers it shares with the decoder; sources and frames are still resident
+    if (h->check_frames) return check_pack(h, n, d_src_base, src_len, d_dst, dst_off, dst_len, status, P.checksum != 0);
     return ZARC_GPU_OK;
+}
+
+// ZARC_GPU_PX_CHECK_FRAMES: decode the frames this pass has assembled (decode-only, into the handle's scratch) and compare the bytes with
+// the sources (zarc_check_compare).  The decoder's timers stay out of h->ms: the call reports pack's.
+int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, uint64_t *dst_len,
+               int *status, bool trailer)
+{
+#ifdef ZARC_GPU_DIAG
+    // fault injection (diagnostic build only): one byte of one assembled frame, between assembly and the check.  The decoder is built to
+    // distrust what it reads; this shows the check failing, which it otherwise never would
+    for (int tail = 0; tail < 2; tail++) {
+        const int idx = diag_env(tail ? "ZARC_GPU_CHECK_FLIP_TAIL" : "ZARC_GPU_CHECK_FLIP_BODY", -1);
+        if (idx < 0 || (size_t)idx >= n || dst_len[idx] == 0) continue;
+        uint8_t *at = (uint8_t *)d_dst + dst_off[idx] + (tail ? dst_len[idx] - 1 : dst_len[idx] / 2), v = 0;
+        ZHIP(hipMemcpy(&v, at, 1, hipMemcpyDeviceToHost));
+        v ^= 0xFF;
+        ZHIP(hipMemcpy(at, &v, 1, hipMemcpyHostToDevice));
+    }
+#endif
+    std::vector<uint32_t> first_bad(n, ZARC_CHECK_CLEAN);
+    h->chk_ms = 0;
+    const PackCheck chk{(const uint8_t *)d_src_base, trailer, 0u, first_bad.data(), &h->chk_ms};
+    const int rc = unpack_device_split(h, n, d_dst, dst_off, dst_len, nullptr, nullptr, src_len, nullptr, nullptr, nullptr, &chk);
+    if (rc) return rc;
+#ifdef ZARC_GPU_DIAG
+    if (diag_env("ZARC_GPU_CHECK_STATS", 0)) fprintf(stderr, "zarc_check_compare: %.3f ms\n", h->chk_ms);
+#endif
+    bool any = false;
+    for (size_t i = 0; i < n; i++) {
+        if (first_bad[i] == ZARC_CHECK_CLEAN) continue;
+        if (!any) { any = true; h->chk_index = i; h->chk_at = first_bad[i]; }
+        if (status) status[i] = ZARC_GPU_FRAME_CORRUPT;
+        dst_len[i] = 0;
+    }
+    if (!any) return ZARC_GPU_OK;
+    check_message(h, h->chk_index);
+    return ZARC_GPU_E_CHECK;
+}
+
+// (the callers above pack_device_impl know an entry by another index: they say it again with theirs)
+void check_message(zarc_gpu_t *h, size_t index)
+{
+    char msg[160];
+    if (h->chk_at == ZARC_CHECK_TRAILER) snprintf(msg, sizeof msg, "read-back check: entry %zu: checksum trailer differs from the XXH64 of its source", index);
+    else snprintf(msg, sizeof msg, "read-back check: entry %zu decodes to other bytes than its source, first at byte %u", index, h->chk_at);
+    h->chk_index = index;
+    set_error(h, msg);
 }
 
 // Hash first (content_frame.rs:26-33): digest every entry, ask the caller which digests it has a frame for already, compress the rest.
@@ -885,8 +978,9 @@ int pack_device_dedup_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, cons
     std::vector<int> st(m);
     for (size_t j = 0; j < m; j++) { off[j] = src_off[keep[j]]; len[j] = src_len[keep[j]]; }
     rc = pack_device_impl(h, m, d_src_base, off.data(), len.data(), d_dst, dst_cap, doff.data(), dlen.data(), nullptr, st.data(), true);
-    if (rc) return rc;
+    if (rc && rc != ZARC_GPU_E_CHECK) return rc;
     for (size_t j = 0; j < m; j++) { dst_off[keep[j]] = doff[j]; dst_len[keep[j]] = dlen[j]; status[keep[j]] = st[j]; }
+    if (rc) { check_message(h, keep[h->chk_index]); return rc; }
     h->ms[ZARC_GPU_T_BLAKE3] = ms_b3;
     h->ms[ZARC_GPU_T_TOTAL] += ms_b3;
     return ZARC_GPU_OK;
@@ -916,23 +1010,30 @@ int zarc_gpu_pack_batch_device_dedup(zarc_gpu_t *h, size_t n, const void *d_src_
 namespace {
 constexpr int UNPACK_SPLIT = -1000; // internal: the decoder's scratch for this batch exceeds the budget, run it in two parts
 
+// own_out: bytes of engine-owned output scratch this call decodes into (verify, read-back check); they count against the budget
 int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off_in, const uint64_t *frame_len_in,
                        void *d_dst_base, const uint64_t *dst_off_in, const uint64_t *raw_len_in, const uint8_t *expect_in, uint8_t *digest,
-                       int *status)
+                       int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr)
 {
     int rc = 0;
+    DevBuf &b_dst_off = chk ? h->d_chk_off : h->d_dst_off;
     uint64_t total_raw = 0;
     for (size_t i = 0; i < n; i++) {
-        if (dst_off_in[i] % ZARC_GPU_ALIGN) { set_error(h, "output offset not 16-byte aligned"); return ZARC_GPU_E_PARAM; }
+        if (dst_off_in && dst_off_in[i] % ZARC_GPU_ALIGN) { set_error(h, "output offset not 16-byte aligned"); return ZARC_GPU_E_PARAM; }
         if (frame_len_in[i] >= 0xFFFFFFF0ull || raw_len_in[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
         total_raw += raw_len_in[i];
     }
     const std::vector<uint32_t> order = diag_env("ZARC_GPU_DEC_DENSITY", 1) ? order_for_decode(raw_len_in, frame_len_in, n) : order_by_size_desc(raw_len_in, n);
     std::vector<uint64_t> frame_off(n), frame_len(n), dst_off(n), raw_len(n);
-    for (size_t i = 0; i < n; i++) { const uint32_t f = order[i]; frame_off[i] = frame_off_in[f]; frame_len[i] = frame_len_in[f]; dst_off[i] = dst_off_in[f]; raw_len[i] = raw_len_in[f]; }
+    if (dst_off_in)
+        for (size_t i = 0; i < n; i++) { const uint32_t f = order[i]; frame_off[i] = frame_off_in[f]; frame_len[i] = frame_len_in[f]; dst_off[i] = dst_off_in[f]; raw_len[i] = raw_len_in[f]; }
+    else { // engine-owned output (verify, read-back check): laid out right here, in the decoder's own order, 16-byte aligned -- own_out bytes in all
+        uint64_t at = 0;
+        for (size_t i = 0; i < n; i++) { const uint32_t f = order[i]; frame_off[i] = frame_off_in[f]; frame_len[i] = frame_len_in[f]; dst_off[i] = at; raw_len[i] = raw_len_in[f]; at += align_up((size_t)raw_len[i], ZARC_GPU_ALIGN); }
+    }
     if ((rc = upload_u64(h, h->d_frame_off, frame_off.data(), n))) return rc;
     if ((rc = upload_u64(h, h->d_frame_len, frame_len.data(), n))) return rc;
-    if ((rc = upload_u64(h, h->d_dst_off, dst_off.data(), n))) return rc;
+    if ((rc = upload_u64(h, b_dst_off, dst_off.data(), n))) return rc;
     if ((rc = upload_u64(h, h->d_raw_len, raw_len.data(), n))) return rc;
     { std::vector<uint32_t> ident(n); std::iota(ident.begin(), ident.end(), 0u); if ((rc = upload_u32(h, h->d_order, ident.data(), n))) return rc; } // the queues walk the (sorted) indices
     const size_t dec_grid = std::min<size_t>(n, (size_t)h->num_cus * 16); // 4 waves per SIMD (launch bounds of the frame kernels: 128 VGPRs, no spills)
@@ -948,7 +1049,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         ZHIP(h->d_expect.reserve(n * 32));
         ZHIP(hipMemcpyAsync(h->d_expect.p, ex, n * 32, hipMemcpyHostToDevice, h->stream));
     }
-    Timer t{h};
+    Timer t{h, chk ? 8 : 0};
     int e0, e1, e3;
     ZHIP(t.mark(&e0));
     // ---- fast path: block scan (lane per frame), then sequence entropy decoding with one lane per block ----
@@ -1022,11 +1123,13 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
           c += r;
       }
       gchunk0[groups] = c; }
-    if ((rc = upload_u64(h, h->d_chunk_prefix, cprefix.data(), cprefix.size()))) return rc;
-    ZHIP(h->d_cvs.reserve(gchunk0[groups] * 32));
-    ZHIP(h->d_cvs_tmp.reserve(gchunk0[groups] * 32));
-    ZHIP(h->d_digests.reserve(n * 32));
-    ZHIP(h->d_xxh.reserve(n * 8));
+    if (!chk) {
+        if ((rc = upload_u64(h, h->d_chunk_prefix, cprefix.data(), cprefix.size()))) return rc;
+        ZHIP(h->d_cvs.reserve(gchunk0[groups] * 32));
+        ZHIP(h->d_cvs_tmp.reserve(gchunk0[groups] * 32));
+        ZHIP(h->d_digests.reserve(n * 32));
+        ZHIP(h->d_xxh.reserve(n * 8));
+    }
     std::vector<uint64_t> seqidx, litidx;
     uint64_t total_seqs = 0, total_lits = 0;
     uint64_t g_seq_at[zarc_gpu::DEC_GROUPS + 1] = {}, g_lit_at[zarc_gpu::DEC_GROUPS + 1] = {}; // lean: the groups' first sequence / literal
@@ -1076,7 +1179,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
             seqidx[nslots] = total; litidx[nslots] = lit_total;
             total_seqs = total; total_lits = lit_total;
         }
-        if (h->scratch_budget && n > 1 && total_seqs * 8 + total_lits + nslots * (uint64_t)(ZDEC_TABLE_CELLS * 2 + sizeof(ZdecBlock) + 32) > h->scratch_budget) return UNPACK_SPLIT;
+        if (h->scratch_budget && n > 1 && own_out + total_seqs * 8 + total_lits + nslots * (uint64_t)(ZDEC_TABLE_CELLS * 2 + sizeof(ZdecBlock) + 32) > h->scratch_budget) return UNPACK_SPLIT;
         if (!lean) {
             if ((rc = upload_u64(h, h->d_seqidx, seqidx.data(), nslots))) return rc;
             if ((rc = upload_u64(h, h->d_litidx, litidx.data(), nslots))) return rc;
@@ -1260,7 +1363,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         if (fastpath) {
             const size_t listed = pieces[g].size(), np = listed + (f1 - fl); // behind the list: frames [fl, f1), one piece each, made up by the kernel
             hipLaunchKernelGGL(zarc_zstd_frames, dim3((unsigned)std::min<size_t>(np, (size_t)h->num_cus * 16)), dim3(64), 0, sa, (const uint8_t *)d_frames_base, h->d_frame_off.as<uint64_t>(),
-                               h->d_frame_len.as<uint64_t>(), (uint8_t *)d_dst_base, h->d_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(),
+                               h->d_frame_len.as<uint64_t>(), (uint8_t *)d_dst_base, b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(),
                                h->d_pieces.as<ZdecPiece>() + piece_base, (uint32_t)listed, (uint32_t)fl, (uint32_t)np, h->d_status.as<int32_t>(), h->d_stored_ck.as<uint32_t>(), dec_dbg, h->d_queue.as<uint32_t>() + 2 * g,
                                h->d_fast.as<uint32_t>(), h->d_slot_prefix.as<uint64_t>(), h->d_zblocks.as<ZdecBlock>(), h->d_seqidx.as<uint64_t>(),
                                h->d_seqs.as<uint64_t>(), h->d_litidx.as<uint64_t>(), h->d_lits.as<uint8_t>());
@@ -1270,24 +1373,25 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         // Each group's launch has its own slice of the per-wave literal scratch.
         hipLaunchKernelGGL(zarc_zstd_decode, dim3((unsigned)grid_g), dim3(64), (size_t)diag_env("ZARC_GPU_DEC_PADLDS", 0), sa,
                            (const uint8_t *)d_frames_base, h->d_frame_off.as<uint64_t>(), h->d_frame_len.as<uint64_t>(), (uint8_t *)d_dst_base,
-                           h->d_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_order.as<uint32_t>() + f0, (uint32_t)ng,
+                           b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_order.as<uint32_t>() + f0, (uint32_t)ng,
                            h->d_declit.as<uint8_t>() + (size_t)g * (dec_grid / (size_t)groups) * (size_t)(ZARC_BLOCK_MAX + 64),
                            h->d_status.as<int32_t>(), h->d_stored_ck.as<uint32_t>(), dec_dbg, h->d_queue.as<uint32_t>() + 2 * g + 1,
                            fastpath ? h->d_fast.as<uint32_t>() : (const uint32_t *)nullptr);
         ZHIP(hipGetLastError());
         ZHIP(hipEventRecord(ev[5], sa));
+        if (chk) { piece_base += pieces[g].size(); continue; } // decode-only: zarc_check_compare judges the bytes
         // verification passes over the decoded bytes (K2 + XXH64 inside libzstd in the reference): checksum (side stream) and digest
         // next to each other
         ZHIP(hipStreamWaitEvent(sb, ev[5], 0));
         ZHIP(hipEventRecord(ev[6], sb));
-        hipLaunchKernelGGL(zarc_xxh64, dim3((unsigned)((ng * 4 + 255) / 256)), dim3(256), 0, sb, (const uint8_t *)d_dst_base, h->d_dst_off.as<uint64_t>() + f0,
+        hipLaunchKernelGGL(zarc_xxh64, dim3((unsigned)((ng * 4 + 255) / 256)), dim3(256), 0, sb, (const uint8_t *)d_dst_base, b_dst_off.as<uint64_t>() + f0,
                            h->d_raw_len.as<uint64_t>() + f0, (uint32_t)ng, h->d_xxh.as<uint64_t>() + f0);
         ZHIP(hipGetLastError());
         ZHIP(hipEventRecord(ev[7], sb));
         ZHIP(hipEventRecord(ev[8], sa));
         {
             const uint64_t chunks = gchunk0[g + 1] - gchunk0[g];
-            hipLaunchKernelGGL(zarc_blake3_chunks, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, sa, (const uint8_t *)d_dst_base, h->d_dst_off.as<uint64_t>() + f0,
+            hipLaunchKernelGGL(zarc_blake3_chunks, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, sa, (const uint8_t *)d_dst_base, b_dst_off.as<uint64_t>() + f0,
                                h->d_raw_len.as<uint64_t>() + f0, h->d_chunk_prefix.as<uint64_t>() + f0 + (size_t)g, (uint32_t)ng, chunks,
                                h->d_cvs.as<uint32_t>() + gchunk0[g] * 8, h->d_digests.as<uint32_t>() + f0 * 8);
             hipLaunchKernelGGL(zarc_blake3_tree, dim3((unsigned)std::min<size_t>(ng, 65535)), dim3(256), 0, sa, h->d_chunk_prefix.as<uint64_t>() + f0 + (size_t)g, (uint32_t)ng,
@@ -1300,6 +1404,31 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     // join: the decode time ends with the last group's frame pass, the whole call with the last hash
     for (int g = 0; g < groups; g++) if (groups > 1) ZHIP(hipStreamWaitEvent(h->stream, h->ev_g[g][5], 0));
     ZHIP(t.mark(&e1));
+    if (chk) {
+        // ---- read-back check: decoded bytes against the pack pass's sources (the frame passes are joined above; with one group they ran
+        // on the engine stream)
+        std::vector<uint64_t> slices(n + 1, 0);
+        for (size_t i = 0; i < n; i++) slices[i + 1] = slices[i] + std::max<uint64_t>(1, (raw_len[i] + ZARC_CHECK_SLICE - 1) / ZARC_CHECK_SLICE);
+        if (slices[n] > 0x7FFFFFFFull) { set_error(h, "read-back check: batch too large"); return ZARC_GPU_E_PARAM; }
+        if ((rc = upload_u64(h, h->d_chk_slices, slices.data(), n + 1))) return rc;
+        if ((rc = upload_u32(h, h->d_chk_order, order.data(), n))) return rc;
+        ZHIP(h->d_chk_bad.reserve(n * 4));
+        ZHIP(hipMemsetAsync(h->d_chk_bad.p, 0xFF, n * 4, h->stream));
+        ZHIP(t.mark(&e3));
+        hipLaunchKernelGGL(zarc_check_compare, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_chk_slices.as<uint64_t>(), h->d_chk_order.as<uint32_t>(),
+                           chk->entry0, (const uint8_t *)d_dst_base, b_dst_off.as<uint64_t>(), h->d_status.as<int32_t>(), chk->src_base, h->d_off.as<uint64_t>(),
+                           h->d_len.as<uint64_t>(), (const uint8_t *)d_frames_base, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>(),
+                           chk->trailer ? h->d_xxh.as<uint64_t>() : (const uint64_t *)nullptr, h->d_chk_bad.as<uint32_t>());
+        ZHIP(hipGetLastError());
+        int e4;
+        ZHIP(t.mark(&e4));
+        std::vector<uint32_t> bad(n);
+        ZHIP(hipMemcpyAsync(bad.data(), h->d_chk_bad.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+        ZHIP(hipStreamSynchronize(h->stream));
+        for (size_t i = 0; i < n; i++) chk->first_bad[order[i]] = bad[i];
+        *chk->ms += elapsed(h, e3, e4);
+        return ZARC_GPU_OK;
+    }
     for (int g = 0; g < groups; g++) {
         ZHIP(hipStreamWaitEvent(h->stream, h->ev_g[g][7], 0));
         if (groups > 1) ZHIP(hipStreamWaitEvent(h->stream, h->ev_g[g][9], 0));
@@ -1357,19 +1486,36 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
 // A batch whose decoder scratch (sequences and literals decoded ahead, tables) does not fit -- the budget of ZARC_GPU_PX_SCRATCH_MB, or
 // the device itself -- is unpacked in two halves, each of which may split again; the scratch is reused between them.  Frames are
 // independent, so nothing changes but the time.
+// d_dst_base == nullptr (verify, the read-back check of pack): the decoded bytes go to scratch the handle owns (d_vout, offsets 16-byte
+// aligned in the decoder's order, made by unpack_device_once: no per-frame array of the caller's is involved) and count against the same budget: a batch whose decoded bytes exceed it is halved before it is tried, one
+// that does not fit the device is halved after; a single frame runs alone whatever its size.
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
-                        void *d_dst_base, const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status)
+                        void *d_dst_base, const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status,
+                        const PackCheck *chk = nullptr)
 {
-    uint64_t total = 0, acc = 0;
-    for (size_t i = 0; i < n; i++) total += raw_len[i];
+    const bool own = d_dst_base == nullptr;
+    uint64_t total = 0, acc = 0, own_bytes = 0;
+    for (size_t i = 0; i < n; i++) { total += raw_len[i]; own_bytes += (raw_len[i] + (ZARC_GPU_ALIGN - 1)) & ~(uint64_t)(ZARC_GPU_ALIGN - 1); }
+    if (!own) own_bytes = 0;
     int rc = UNPACK_SPLIT;
-    if (!(n >= 2 && h->dec_split_above && total >= h->dec_split_above)) // (a batch of this size ran out of device memory before: do not try again)
-        rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, d_dst_base, dst_off, raw_len, expect, digest, status);
+    bool attempt = !(n >= 2 && h->dec_split_above && total >= h->dec_split_above); // (a batch of this size ran out of device memory before: do not try again)
+    if (own && attempt) {
+        if (n >= 2 && h->scratch_budget && own_bytes > h->scratch_budget) attempt = false;
+        else {
+            const hipError_t e = h->d_vout.reserve(own_bytes + ZARC_GPU_PAD + 256);
+            if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); rc = ZARC_GPU_E_NOMEM; attempt = false; }
+            else ZHIP(e);
+        }
+    }
+    if (attempt)
+        rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, own ? h->d_vout.p : d_dst_base, own ? nullptr : dst_off, raw_len, expect, digest,
+                                status, own_bytes, chk);
     if ((rc != UNPACK_SPLIT && rc != ZARC_GPU_E_NOMEM) || n < 2) return rc == UNPACK_SPLIT ? ZARC_GPU_E_NOMEM : rc;
     (void)hipStreamSynchronize(h->stream);
     if (rc == ZARC_GPU_E_NOMEM) {
-        DevBuf *big[] = {&h->d_seqs, &h->d_lits, &h->d_ztables, &h->d_zblocks, &h->d_cvs, &h->d_cvs_tmp, &h->d_seqidx, &h->d_litidx, &h->d_nseq};
+        DevBuf *big[] = {&h->d_seqs, &h->d_lits, &h->d_ztables, &h->d_zblocks, &h->d_seqidx, &h->d_litidx, &h->d_nseq, &h->d_vout};
         for (DevBuf *b : big) b->release();
+        if (!chk) { h->d_cvs.release(); h->d_cvs_tmp.release(); }
         if (!h->dec_split_above || total < h->dec_split_above) h->dec_split_above = total;
     }
     size_t k = 0;
@@ -1380,12 +1526,14 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
     for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] = 0;
     for (int p = 0; p < 2; p++) {
         const size_t a = part[p], m = part[p + 1] - a;
-        rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
-                                 digest + a * 32, status + a);
+        PackCheck sub{};
+        if (chk) { sub = *chk; sub.entry0 += (uint32_t)a; sub.first_bad += a; }
+        rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
+                                 digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr);
         if (rc) return rc;
         for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] += h->ms[i];
     }
-    for (int i = 0; i < ZARC_GPU_T_COUNT; i++) h->ms[i] = ms[i];
+    if (!chk) for (int i = 0; i < ZARC_GPU_T_COUNT; i++) h->ms[i] = ms[i];
     return ZARC_GPU_OK;
 }
 } // namespace
@@ -1400,6 +1548,17 @@ int zarc_gpu_unpack_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_b
     if (n == 0) return ZARC_GPU_OK;
     if (!d_frames_base || !frame_off || !frame_len || !d_dst_base || !dst_off || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
     return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, d_dst_base, dst_off, raw_len, expect, digest, status);
+}
+
+// FrameIterator::verify() without the bytes: the same decoder, hash passes and verdict as unpack, the output in scratch of the handle
+int zarc_gpu_verify_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                 const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status);
 }
 
 // ---- host-memory entry points: stage through engine-owned arenas -----------------------------------
@@ -1480,6 +1639,15 @@ bool segs_pinned(const std::vector<Seg> &segs, uint64_t min_run)
     return true;
 }
 
+// content bytes a copy helper has moved (zarc_gpu_last_copy_bytes): the segments' own lengths, not the padding between them
+inline void count_copy(zarc_gpu *h, const std::vector<Seg> &segs, bool to_device, bool direct)
+{
+    uint64_t bytes = 0;
+    for (const Seg &sg : segs) bytes += sg.len;
+    h->copy_bytes[to_device ? ZARC_GPU_C_H2D : ZARC_GPU_C_D2H].fetch_add(bytes, std::memory_order_relaxed);
+    h->copy_bytes[direct ? ZARC_GPU_C_DIRECT : ZARC_GPU_C_RING].fetch_add(bytes, std::memory_order_relaxed);
+}
+
 // pinned caller memory <-> device range at `dev_base`: one asynchronous copy per run of segments that are contiguous on both sides
 int direct_copy(zarc_gpu *h, hipStream_t stream, const std::vector<Seg> &segs, uint8_t *dev_base, bool to_device)
 {
@@ -1493,9 +1661,10 @@ int direct_copy(zarc_gpu *h, hipStream_t stream, const std::vector<Seg> &segs, u
         // back to the staging ring, which redoes the whole range (copies already queued here move the same bytes).
         const hipError_t e_ = to_device ? hipMemcpyAsync(dev_base + segs[k].dev, segs[k].host, len, hipMemcpyHostToDevice, stream)
                                         : hipMemcpyAsync(segs[k].host, dev_base + segs[k].dev, len, hipMemcpyDeviceToHost, stream);
-        if (e_ != hipSuccess) { (void)hipGetLastError(); (void)h; return 1; }
+        if (e_ != hipSuccess) { (void)hipGetLastError(); return 1; }
         k = e;
     }
+    count_copy(h, segs, to_device, /*direct=*/true); // (a refused run returns above: the ring redoes the range and counts it)
     return 0;
 }
 
@@ -1515,6 +1684,7 @@ int staged_h2d(zarc_gpu *h, hipStream_t stream, const std::vector<Seg> &segs, ui
         ZHIP(hipMemcpyAsync(dev_base + lo, h->pin[slot], hi - lo, hipMemcpyHostToDevice, stream));
         ZHIP(hipEventRecord(h->pin_ev[slot], stream));
     }
+    count_copy(h, segs, true, /*direct=*/false);
     return 0;
 }
 
@@ -1544,6 +1714,7 @@ int staged_d2h(zarc_gpu *h, hipStream_t stream, const std::vector<Seg> &segs, co
         have_prev = true;
     }
     if (have_prev) { ZHIP(hipEventSynchronize(h->pin_ev[prev.slot])); piece_copy(segs, prev.first, prev.lo, prev.hi, h->pin[prev.slot], false, (unsigned)h->copy_threads); }
+    count_copy(h, segs, false, /*direct=*/false);
     return 0;
 }
 
@@ -1597,6 +1768,7 @@ int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const
         total += align_up(len[i], ZARC_GPU_ALIGN);
     }
     ZHIP(h->d_arena_in.reserve(total + ZARC_GPU_PAD + 256));
+    NestedCall nested(h);
     if ((rc = staged_h2d(h, h->stream, segs, h->d_arena_in.as<uint8_t>(), total))) return rc;
     return zarc_gpu_blake3_batch_device(h, n, h->d_arena_in.p, off.data(), l64.data(), (uint8_t *)digest);
 }
@@ -1614,6 +1786,7 @@ int zarc_gpu_pack_batch_dedup(zarc_gpu_t *h, size_t n, const void *const *src, c
     if (rc) return rc;
     if (n == 0) return ZARC_GPU_OK;
     if (!src || !src_len || !dst || !dst_off || !dst_len || !digest || (known && !status)) return ZARC_GPU_E_PARAM;
+    NestedCall nested(h);
     std::vector<uint64_t> in_sz(n), out_sz(n), l64(n);
     uint64_t need = 0;
     for (size_t i = 0; i < n; i++) {
@@ -1690,6 +1863,10 @@ int zarc_gpu_pack_batch_dedup(zarc_gpu_t *h, size_t n, const void *const *src, c
                                     dlen.data() + i0, (uint8_t *)digest[i0], status ? status + i0 : nullptr, known ? (zarc_gpu_known_fn)shifted : nullptr, &shift);
         if (helper.joinable()) helper.join();
         if (helper_out.joinable()) helper_out.join();
+        if (rc == ZARC_GPU_E_CHECK) { // the batch's output is void: say which entry of the batch it was
+            for (size_t k = 0; k < m; k++) dst_len[i0 + k] = (size_t)dlen[i0 + k];
+            check_message(h, i0 + h->chk_index);
+        }
         if (rc) return rc;
         if (helper_rc) return helper_rc;
         if (helper_rc_out) return helper_rc_out;
@@ -1709,6 +1886,7 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
     if (rc) return rc;
     if (n == 0) return ZARC_GPU_OK;
     if (!frame || !frame_len || !raw_len || !dst || !digest || !status) return ZARC_GPU_E_PARAM;
+    NestedCall nested(h);
     std::vector<uint64_t> in_sz(n), out_sz(n), weight(n), flen(n), rlen(n);
     for (size_t i = 0; i < n; i++) {
         if ((frame_len[i] && !frame[i]) || (raw_len[i] && !dst[i])) return ZARC_GPU_E_PARAM;
@@ -1777,6 +1955,67 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
     }
     if ((rc = copy_out(cs.size() - 1))) return rc;
     ZHIP(hipStreamSynchronize(side_out));
+    for (int t = 0; t < ZARC_GPU_T_COUNT; t++) h->ms[t] = sum[t];
+    return ZARC_GPU_OK;
+}
+
+// The chunk loop of zarc_gpu_unpack_batch without its outbound half: chunk c+1's frames come in while chunk c is decoded and judged;
+// nothing but statuses and digests goes back.  A chunk's decoded bytes live in the handle's scratch (unpack_device_split), so the
+// chunks are cut by the same weight as unpack's.
+int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                          const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    NestedCall nested(h);
+    std::vector<uint64_t> in_sz(n), out_sz(n), weight(n), flen(n), rlen(n);
+    for (size_t i = 0; i < n; i++) {
+        if (frame_len[i] && !frame[i]) return ZARC_GPU_E_PARAM;
+        if ((uint64_t)frame_len[i] >= 0xFFFFFFF0ull || (uint64_t)raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; } // before any size arithmetic or staging
+        flen[i] = frame_len[i]; rlen[i] = raw_len[i];
+        in_sz[i] = align_up(frame_len[i], ZARC_GPU_ALIGN);
+        out_sz[i] = align_up(raw_len[i], ZARC_GPU_ALIGN);
+        weight[i] = std::max(in_sz[i], out_sz[i]);
+    }
+    const std::vector<Chunk> cs = make_chunks(n, in_sz, out_sz, weight, h->stage_chunk ? h->stage_chunk : (uint64_t)4 << 30);
+    uint64_t max_in = 0;
+    for (const Chunk &c : cs) max_in = std::max(max_in, c.in_bytes);
+    const uint64_t in_half = align_up(max_in + ZARC_GPU_PAD + 256, 256);
+    ZHIP(h->d_arena_in.reserve(2 * in_half));
+    uint8_t *const ain = h->d_arena_in.as<uint8_t>();
+    const int device = h->device;
+    hipStream_t side = h->stream_stage;
+    auto copy_in = [&](size_t c) -> int {
+        std::vector<Seg> segs;
+        uint64_t at = 0;
+        for (size_t i = cs[c].i0; i < cs[c].i1; i++) { if (frame_len[i]) segs.push_back(Seg{(uint8_t *)frame[i], at, frame_len[i]}); at += in_sz[i]; }
+        return staged_h2d(h, side, segs, ain + (c & 1) * in_half, at);
+    };
+    float sum[ZARC_GPU_T_COUNT] = {};
+    if ((rc = copy_in(0))) return rc;
+    ZHIP(hipStreamSynchronize(side));
+    for (size_t c = 0; c < cs.size(); c++) {
+        int helper_rc = 0;
+        auto move_in = [&] {
+            (void)hipSetDevice(device);
+            if (c + 1 < cs.size()) helper_rc = copy_in(c + 1);
+            if (hipStreamSynchronize(side) != hipSuccess) helper_rc = ZARC_GPU_E_DEVICE;
+        };
+        std::thread helper;
+        if (h->stage_thread) helper = std::thread(move_in); else move_in();
+        const size_t m = cs[c].i1 - cs[c].i0, i0 = cs[c].i0;
+        std::vector<uint64_t> foff(m);
+        uint64_t fa = 0;
+        for (size_t k = 0; k < m; k++) { foff[k] = fa; fa += in_sz[i0 + k]; }
+        rc = zarc_gpu_verify_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
+                                          expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0);
+        if (helper.joinable()) helper.join();
+        if (rc) return rc;
+        if (helper_rc) return helper_rc;
+        for (int t = 0; t < ZARC_GPU_T_COUNT; t++) sum[t] += h->ms[t] > 0 ? h->ms[t] : 0;
+    }
     for (int t = 0; t < ZARC_GPU_T_COUNT; t++) h->ms[t] = sum[t];
     return ZARC_GPU_OK;
 }

@@ -181,9 +181,17 @@ __global__ void zarc_zdec_seqs_shared32(const uint8_t *frames_base, const uint64
 __global__ void zarc_zdec_seqs_shared16(const uint8_t *frames_base, const uint64_t *frame_off, uint64_t n_slots, const uint64_t *slot_prefix,
                                         ZdecBlock *zblocks, const uint64_t *seq_index, uint64_t *seqs, uint32_t *fast, uint64_t slot_base,
                                         uint32_t *wave_flag);
-// status[i]: keeps decode errors; else CHECKSUM if the stored XXH64 differs; else DIGEST if expect differs
-__global__ void zarc_unpack_verdict(uint32_t n, const uint64_t *xxh, const uint32_t *stored_checksum, const uint32_t *digests,
+// status[i]: keeps decode errors (and clears the digest of such a frame); else CHECKSUM if the stored XXH64 differs; else DIGEST if expect differs
+__global__ void zarc_unpack_verdict(uint32_t n, const uint64_t *xxh, const uint32_t *stored_checksum, uint32_t *digests,
                                     const uint32_t *expect /* may be null */, int32_t *status);
+// read-back check of a pack call (zge_check.hip): decoded bytes against source bytes, a workgroup per (frame, slice); arrays without a
+// note are in the decoder's order, the others are the pack call's own (indexed by entry0 + entry_of[i]).  first_bad[i] (start:
+// ZARC_CHECK_CLEAN) receives the lowest differing byte offset, or ZARC_CHECK_TRAILER when only the checksum trailer differs
+constexpr uint32_t ZARC_CHECK_SLICE = 65536, ZARC_CHECK_CLEAN = 0xFFFFFFFFu, ZARC_CHECK_TRAILER = 0xFFFFFFFEu;
+__global__ void zarc_check_compare(uint32_t n, const uint64_t *slice_prefix, const uint32_t *entry_of, uint32_t entry0, const uint8_t *dec_base,
+                                   const uint64_t *dec_off, const int32_t *dec_status, const uint8_t *src_base, const uint64_t *src_off /* pack */,
+                                   const uint64_t *src_len /* pack */, const uint8_t *frame_base, const uint64_t *frame_off /* pack */,
+                                   const uint64_t *frame_len /* pack */, const uint64_t *xxh /* pack; null = no trailer to look at */, uint32_t *first_bad);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

@@ -1,4 +1,4 @@
-// zarc_amd/csrc/zge_assemble.hip -- encoder stage 3 (frame assembly), unpack verdicts, corpus fill.
+// zarc_amd/csrc/zge_assemble.hip -- encoder stage 3 (frame assembly), read-back compare (zge_check.hip), unpack verdicts, corpus fill.
 //
 // Frame layout written here (RFC 8878 3.1.1; field order as crates/ozarc/src/framing.rs:106-278):
 //   magic 28 B5 2F FD | descriptor | [window byte] | frame content size | blocks ... | [XXH64 low 32, LE]
@@ -139,6 +139,8 @@ __global__ void __launch_bounds__(256) zarc_gather(const uint8_t *__restrict__ s
     for (uint64_t at = 0; at < l; at += 0x40000000ull) group_copy(d + at, s + at, (uint32_t)(l - at > 0x40000000ull ? 0x40000000ull : l - at), (int)threadIdx.x, (int)blockDim.x);
 }
 
+#include "zge_check.hip" // zarc_check_compare: the read-back check of a pack call
+
 // Store mode (Encoder::enable_compression(false), crates/zarc/src/encode.rs:95-97 -> write_uncompressed_frame,
 // encode/lowlevel_frames.rs:47-84): the content goes into Raw blocks.  Like the reference's frame this one carries an
 // 8-byte Frame_Content_Size, no Single_Segment flag and no checksum -- but it also carries the Window_Descriptor that
@@ -178,12 +180,17 @@ __global__ void __launch_bounds__(256) zarc_zge_store(const uint8_t *__restrict_
 // status[i] keeps a decode error; otherwise CHECKSUM when the stored XXH64 differs (what libzstd reports as
 // "Restored data doesn't match checksum"); otherwise DIGEST when the BLAKE3 differs from `expect` -- which the
 // reference only logs (crates/zarc-cli/src/unpack.rs:118-120), so the bytes are delivered either way.
+// A frame that did not decode has no content to digest: the hash pass ran over whatever its output range held before, so its digest
+// is cleared here (all zero) -- unpack and verify, whose output ranges have different histories, then report the same.
 __global__ void zarc_unpack_verdict(uint32_t n, const uint64_t *__restrict__ xxh, const uint32_t *__restrict__ stored_checksum,
-                                    const uint32_t *__restrict__ digests, const uint32_t *__restrict__ expect, int32_t *__restrict__ status)
+                                    uint32_t *__restrict__ digests, const uint32_t *__restrict__ expect, int32_t *__restrict__ status)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    if (status[i] != ZARC_FRAME_OK) return;
+    if (status[i] != ZARC_FRAME_OK) {
+        for (int w = 0; w < 8; w++) digests[(uint64_t)i * 8 + w] = 0;
+        return;
+    }
     if (stored_checksum[2 * i] && (uint32_t)xxh[i] != stored_checksum[2 * i + 1]) { status[i] = ZARC_FRAME_CHECKSUM; return; }
     if (expect) {
         uint32_t diff = 0; // constant-time compare, like integrity.rs:17-22

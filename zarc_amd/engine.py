@@ -62,6 +62,10 @@ class Engine:
     def kernel_ms(self, which):
         return float(self.lib.zarc_gpu_last_kernel_ms(self.h, which))
 
+    def copy_bytes(self, which):
+        """Content bytes the most recent batch call moved (_lib.C_H2D / C_D2H / C_RING / C_DIRECT); device forms report 0."""
+        return int(self.lib.zarc_gpu_last_copy_bytes(self.h, which))
+
     # ---- device memory helpers ----
     def malloc(self, nbytes):
         p = ctypes.c_void_p()
@@ -130,6 +134,23 @@ class Engine:
             exp = np.ascontiguousarray(expect, dtype=np.uint8)
         self._check(self.lib.zarc_gpu_unpack_batch_device(
             self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, ctypes.c_void_p(d_dst), pdo, prl,
+            exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return dig, status
+
+    def verify_device(self, d_frames, frame_off, frame_len, raw_len, expect=None):
+        """unpack_device without an output: -> (digests, statuses), exactly unpack's."""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        self._check(self.lib.zarc_gpu_verify_batch_device(
+            self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl,
             exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
             dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return dig, status
@@ -228,3 +249,21 @@ class Engine:
                                                    exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
                                                    dig.ctypes.data_as(ctypes.c_void_p), status))
         return [(bytes(outs[i][:int(raw_lens[i])]), bytes(dig[i]), int(status[i])) for i in range(n)]
+
+    def verify(self, frames, raw_lens, expect=None):
+        """-> list of (digest, status): FrameIterator::verify for a batch.  What unpack() reports for the same frames, without the bytes:
+        only the compressed frames cross to the device and nothing but 36 bytes per frame comes back."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        self._check(self.lib.zarc_gpu_verify_batch(self.h, n, ptrs, lens, rl,
+                                                   exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+                                                   dig.ctypes.data_as(ctypes.c_void_p), status))
+        return [(bytes(dig[i]), int(status[i])) for i in range(n)]

@@ -179,10 +179,14 @@ bool safe_name(const std::vector<std::string> &name)
 
 int usage()
 {
-    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|list-files> ...\n"
-                         "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] [--split-blocks] PATH...\n"
+    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|list-files> ...\n"
+                         "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] [--split-blocks] [--check] PATH...\n"
                          "         --split-blocks  cut 64 KiB blocks where their statistics change (smaller frames on binaries / JSON; off by default)\n"
+                         "         --check         decode every frame again on the device and compare it with its file before it is written; a mismatch\n"
+                         "                         ends the run with exit status 1 and no directory or trailer is written (off by default)\n"
                          "       zarc unpack INPUT [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
+                         "       zarc verify INPUT [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
+                         "         tests the content frames of the files (each distinct frame once) without writing anything; exit status 0 iff all are good\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -317,7 +321,7 @@ int cmd_pack(const std::vector<std::string> &a)
     std::string output;
     std::vector<std::string> paths;
     std::vector<ZstdParam> params;
-    bool store = false, follow = false, have_level = false, split_blocks = false;
+    bool store = false, follow = false, have_level = false, split_blocks = false, check = false;
     int level = 0, gpus = 1;
     for (size_t i = 0; i < a.size(); i++) {
         if (a[i] == "--output" && i + 1 < a.size()) output = a[++i];
@@ -328,6 +332,7 @@ int cmd_pack(const std::vector<std::string> &a)
         else if (a[i] == "-L" || a[i] == "--follow-symlinks") follow = true;
         else if (a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str()); // engine extension: deal every batch to N devices
         else if (a[i] == "--split-blocks") split_blocks = true;                          // engine extension: ZARC_GPU_PX_BLOCK_SPLIT
+        else if (a[i] == "--check") check = true;                                        // engine extension: ZARC_GPU_PX_CHECK_FRAMES
         else if (!a[i].empty() && a[i][0] == '-') return usage();
         else paths.push_back(a[i]);
     }
@@ -354,6 +359,7 @@ int cmd_pack(const std::vector<std::string> &a)
         }
     if (store) enc.enable_compression(false);
     if (split_blocks) enc.split_blocks(true);
+    if (check) enc.check_frames(true);
 
     std::vector<Walked> entries;
     for (const auto &p : paths) walk(p, follow, entries);
@@ -422,7 +428,16 @@ int cmd_pack(const std::vector<std::string> &a)
         std::vector<size_t> len;
         for (auto &c : b.contents) { ptr.push_back(c.data()); len.push_back(c.size()); }
         LOGF(3, "add_data_frames", "entries=%zu files=%zu", b.last - b.first, ptr.size());
-        const std::vector<zarc::Digest> dig = enc.add_data_frames(ptr.data(), len.data(), ptr.size());
+        std::vector<zarc::Digest> dig;
+        try {
+            dig = enc.add_data_frames(ptr.data(), len.data(), ptr.size());
+        } catch (const zarc::Error &e) {
+            // --check: a frame did not decode back to its file.  Nothing of the batch has been written and neither directory nor trailer
+            // will be: what is left at --output is not a zarc archive
+            if (e.code != ZARC_GPU_E_CHECK || !enc.check_failed()) throw;
+            std::fprintf(stderr, "Error: %s: %s\n", entries[b.owner[*enc.check_failed()]].path.c_str(), e.what());
+            return 1;
+        }
         size_t k = 0;
         for (size_t i = b.first; i < b.last; i++) {
             zarc::File f = build_file_with_metadata(entries[i]);
@@ -608,6 +623,79 @@ int cmd_unpack(const std::vector<std::string> &a)
     return 0;
 }
 
+// `zarc verify`: is this archive good?  Every distinct content frame behind the files that pass the filters is decoded and judged on the
+// device exactly as unpack would judge it (zarc_gpu_verify_batch), and nothing is created, opened or changed in the file system.
+int cmd_verify(const std::vector<std::string> &a)
+{
+    std::string input, verify;
+    std::vector<std::regex> filters;
+    int gpus = 1;
+    for (size_t i = 0; i < a.size(); i++) {
+        if (a[i] == "--filter" && i + 1 < a.size()) filters.emplace_back(a[++i]);
+        else if (a[i] == "--verify" && i + 1 < a.size()) verify = a[++i];
+        else if (a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str());
+        else if (!a[i].empty() && a[i][0] == '-') return usage();
+        else input = a[i];
+    }
+    if (input.empty() || gpus < 1 || gpus > 64) return usage();
+    if (gpus > zarc_gpu_device_count()) { std::fprintf(stderr, "Error: --gpus %d but %d device(s) are usable\n", gpus, zarc_gpu_device_count()); return 1; }
+    Mapped m(input);
+    std::vector<int> devices;
+    for (int d = 0; d < gpus; d++) devices.push_back(d);
+    zarc::ArchiveReader rd(m.p, m.n, devices);
+    const std::string digest = base64(rd.trailer().digest.bytes.data(), 32);
+    if (!verify.empty()) {
+        if (verify != digest) { std::fprintf(stderr, "Error: integrity failure: zarc file digest is %s\n", digest.c_str()); return 1; }
+    } else std::fprintf(stderr, "digest: %s\n", digest.c_str());
+    // the files of every distinct frame: a frame is checked ONCE however many files share it
+    std::map<zarc::Digest, std::vector<size_t>> files_of;
+    std::vector<zarc::Digest> order;
+    unsigned long long n_files = 0, failed = 0, bytes = 0;
+    for (size_t i = 0; i < rd.files().size(); i++) {
+        const zarc::File &f = rd.files()[i];
+        if (!f.is_normal() || !passes(filters, to_path(f.name))) continue;
+        n_files++;
+        if (!rd.frames().count(*f.digest)) { // an archive test that shrugs at a missing frame is no test
+            std::fprintf(stderr, "WARN frame not found path=%s\n", to_path(f.name).c_str());
+            failed++;
+            continue;
+        }
+        auto &v = files_of[*f.digest];
+        if (v.empty()) order.push_back(*f.digest);
+        v.push_back(i);
+    }
+    const size_t BATCH = (size_t)1 << 30;
+    std::vector<zarc::Digest> batch;
+    size_t batch_bytes = 0;
+    auto flush = [&]() {
+        if (batch.empty()) return;
+        const std::vector<zarc::FrameReader::Result> res = rd.check_frames(batch);
+        for (size_t k = 0; k < batch.size(); k++) {
+            const bool decoded = res[k].status == ZARC_GPU_FRAME_OK || res[k].status == ZARC_GPU_FRAME_DIGEST;
+            if (decoded && res[k].verify.value_or(false)) continue;
+            for (size_t i : files_of[batch[k]]) {
+                const std::string path = to_path(rd.files()[i].name);
+                if (decoded) std::fprintf(stderr, "ERROR frame verification failed! path=%s\n", path.c_str()); // the text unpack prints (unpack.rs:118-120)
+                else std::fprintf(stderr, "ERROR %s path=%s\n", zarc_gpu_frame_status_name(res[k].status), path.c_str());
+                failed++;
+            }
+        }
+        LOGF(3, "check_frames", "frames=%zu bytes=%zu", batch.size(), batch_bytes);
+        batch.clear();
+        batch_bytes = 0;
+    };
+    for (const zarc::Digest &d : order) {
+        const uint64_t u = rd.frames().at(d).uncompressed;
+        batch.push_back(d);
+        batch_bytes += (size_t)u;
+        bytes += u;
+        if (batch_bytes >= BATCH) flush();
+    }
+    flush();
+    std::fprintf(stderr, "verified %llu files (%zu frames, %llu bytes), %llu failed\n", n_files, order.size(), bytes, failed);
+    return failed ? 1 : 0;
+}
+
 int cmd_list_files(const std::vector<std::string> &a)
 {
     std::string input;
@@ -648,7 +736,7 @@ int main(int argc, char **argv)
         else if (a == "--log-file") {
             have_log_file = true;
             // num_args = 0..=1: a following word that is not a subcommand is the path
-            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
+            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
         } else break;
     }
     if (i >= argc) return usage();
@@ -660,6 +748,7 @@ int main(int argc, char **argv)
         if (!verb.empty() && std::string("pack").rfind(verb, 0) == 0) return cmd_pack(rest);
         if (!verb.empty() && std::string("unpack").rfind(verb, 0) == 0) return cmd_unpack(rest);
         if (!verb.empty() && std::string("list-files").rfind(verb, 0) == 0) return cmd_list_files(rest);
+        if (!verb.empty() && std::string("verify").rfind(verb, 0) == 0) return cmd_verify(rest);
         return usage();
     } catch (const zarc::Error &e) {
         std::fprintf(stderr, "Error: %s\n", e.what());

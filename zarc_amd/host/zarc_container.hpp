@@ -405,6 +405,26 @@ class ArchiveReader {
         return reader_.read_content_frames(data_, len_, wanted);
     }
 
+    // FrameIterator::verify() for the content frames of these digests, without their bytes (FrameReader::check_content_frames): one
+    // result per digest, in order; a digest without a frame record is an error of the caller
+    std::vector<FrameReader::Result> check_frames(const std::vector<Digest> &digests)
+    {
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.check_content_frames(data_, len_, wanted);
+    }
+    // ... for every frame of the directory, in the order of frames()
+    std::vector<FrameReader::Result> check_frames()
+    {
+        std::vector<Digest> all;
+        for (const auto &kv : frames_) all.push_back(kv.first);
+        return check_frames(all);
+    }
+
   private:
     void parse_directory(const std::vector<uint8_t> &dir)
     {

@@ -145,6 +145,9 @@ class Encoder {
     // Engine extension (`zarc pack --split-blocks`): 64 KiB blocks are cut where their literal statistics change
     // (ZARC_GPU_PX_BLOCK_SPLIT).  Set on every handle, so several devices write the archive one would.
     void split_blocks(bool on) { set_zstd_parameter(ZARC_GPU_PX_BLOCK_SPLIT, on ? 1 : 0); }
+    // Engine extension (`zarc pack --check`): every frame is decoded again and compared with its source before the batch call returns
+    // (ZARC_GPU_PX_CHECK_FRAMES); a frame that fails makes add_data_frames throw Error(ZARC_GPU_E_CHECK) and nothing of the batch is written
+    void check_frames(bool on) { set_zstd_parameter(ZARC_GPU_PX_CHECK_FRAMES, on ? 1 : 0); }
 
     // Encoder::add_data_frame for one entry (content_frame.rs:20)
     Digest add_data_frame(const uint8_t *content, size_t len)
@@ -162,6 +165,7 @@ class Encoder {
     std::vector<Digest> add_data_frames(const void *const *content, const size_t *len, size_t n)
     {
         std::vector<Digest> digests(n);
+        check_failed_.reset();
         if (n == 0) return digests;
         // 1. one fresh session per frame (reset(SessionOnly), content_frame.rs:37-39) == one independent frame each.  The batch
         //    is dealt to the devices; every device packs its share into its own buffer, concurrently, with no exchange.
@@ -196,6 +200,10 @@ class Encoder {
             buffers[d].resize(cap);
             rc[d] = zarc_gpu_pack_batch_dedup(engines_[d]->get(), m, src.data(), l.data(), buffers[d].data(), cap, off.data(), out_len.data(),
                                               (uint8_t(*)[32])dig.data(), st.data(), hash_first_ ? (zarc_gpu_known_fn)claim : nullptr, &claims);
+            if (rc[d] == ZARC_GPU_E_CHECK) { // which entry of the CALL it was (the engine's message counts inside this device's share)
+                std::lock_guard<std::mutex> lk(made_mu);
+                for (size_t j = 0; j < m; j++) if (st[j] == ZARC_GPU_FRAME_CORRUPT && (!check_failed_ || idx[j] < *check_failed_)) check_failed_ = idx[j];
+            }
             if (rc[d] != ZARC_GPU_OK) return;
             std::lock_guard<std::mutex> lk(made_mu);
             for (size_t j = 0; j < m; j++) {
@@ -236,6 +244,8 @@ class Encoder {
     // hash-first dedup (default on; off = every entry is compressed and duplicates are dropped afterwards: same archive, more work)
     void set_hash_first(bool on) { hash_first_ = on; }
 
+    // after add_data_frames threw Error(ZARC_GPU_E_CHECK): the first entry of that call whose frame failed its read-back check
+    std::optional<size_t> check_failed() const { return check_failed_; }
     const std::map<Digest, Frame> &frames() const { return frames_; }
     const std::vector<Digest> &frame_order() const { return order_; } // insertion order (the reference uses a HashMap)
     uint64_t offset() const { return offset_; }
@@ -246,6 +256,7 @@ class Encoder {
     Engine &engine0() { return *engines_[0]; }
     uint16_t edition_ = 1;
     bool hash_first_ = true;
+    std::optional<size_t> check_failed_;
     std::map<Digest, Frame> frames_;
     std::vector<Digest> order_;
     uint64_t offset_ = 0;
@@ -277,6 +288,19 @@ class FrameReader {
     // `archive` is the whole file; `wanted` are directory records (offset/length/uncompressed/digest).
     std::vector<Result> read_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted)
     {
+        return run_frames(archive, archive_len, wanted, true);
+    }
+    // FrameIterator::verify() (frame_iterator.rs:83-88) for a batch WITHOUT the bytes: {digest, verify, status} of every frame exactly
+    // as read_content_frames reports them, `data` left empty.  The same record checks, the same dealing over the handles; only the
+    // compressed frames travel to the devices and nothing but statuses and digests comes back (zarc_gpu_verify_batch).
+    std::vector<Result> check_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted)
+    {
+        return run_frames(archive, archive_len, wanted, false);
+    }
+
+  private:
+    std::vector<Result> run_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, bool with_data)
+    {
         const size_t n = wanted.size();
         std::vector<Result> out(n);
         std::vector<size_t> rl(n);
@@ -286,7 +310,7 @@ class FrameReader {
             if (wanted[i].uncompressed >= 0xFFFFFFF0ull || wanted[i].length >= 0xFFFFFFF0ull) throw Error(ZARC_GPU_E_UNSUPPORTED, "frames of 4 GiB or more are not supported");
             // Zstandard cannot expand a frame by more than a factor of ~(128 KiB block from a 4-byte RLE block): a larger claim is corrupt
             if (wanted[i].uncompressed > (wanted[i].length + 16) * (uint64_t)65536) throw Error(ZARC_GPU_E_PARAM, "frame claims an impossible uncompressed size");
-            out[i].data.resize(wanted[i].uncompressed);
+            if (with_data) out[i].data.resize(wanted[i].uncompressed);
             rl[i] = wanted[i].uncompressed;
         }
         if (n == 0) return out;
@@ -306,8 +330,10 @@ class FrameReader {
                 const Frame &f = wanted[idx[j]];
                 fp[j] = archive + f.offset; fl[j] = f.length; ul[j] = f.uncompressed; dp[j] = out[idx[j]].data.data(); expect[j] = f.digest;
             }
-            rc[d] = zarc_gpu_unpack_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), dp.data(), (const uint8_t(*)[32])expect.data(),
-                                          (uint8_t(*)[32])got.data(), status.data());
+            rc[d] = with_data ? zarc_gpu_unpack_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), dp.data(), (const uint8_t(*)[32])expect.data(),
+                                                      (uint8_t(*)[32])got.data(), status.data())
+                              : zarc_gpu_verify_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
+                                                      (uint8_t(*)[32])got.data(), status.data());
             if (rc[d] != ZARC_GPU_OK) return;
             for (size_t j = 0; j < m; j++) {
                 Result &r = out[idx[j]];
@@ -328,7 +354,6 @@ class FrameReader {
         return out;
     }
 
-  private:
     std::vector<std::unique_ptr<Engine>> engines_; // one per device
 };
 
