@@ -12,6 +12,9 @@
  *            ZstdFrameIterator::decompress_step crates/zarc/src/decode/zstd_iterator.rs:88-153
  *   verify : FrameIterator::verify for a batch, without the bytes   crates/zarc/src/decode/frame_iterator.rs:83-88 (and what
  *            `zarc unpack` does with its answer, crates/zarc-cli/src/unpack.rs:118-120)
+ *   repack : Decoder::read_content_frame        crates/zarc/src/decode/frame_iterator.rs:14-27   joined on the device to
+ *            Encoder::add_data_frame            crates/zarc/src/encode/content_frame.rs:20-60    (the reference has no such call: it
+ *            would read every entry out and add it again)
  *   digest : DigestType::verify_data            crates/zarc/src/integrity.rs:107-117
  *   ctx    : CCtx::try_create / init(0) / set_parameter / reset     crates/zarc/src/encode.rs:58-97
  *            DCtx::try_create                   crates/zarc/src/decode/zstd_iterator.rs:29
@@ -39,7 +42,8 @@ extern "C" {
 #define ZARC_GPU_ABI_VERSION 2 /* 2: round 3's entry points (device_count, *_dedup, FRAME_DUPLICATE, PX_ZERO_COPY) + round 4's (warnings, levels).
                                   zarc_gpu_verify_batch*, zarc_gpu_last_copy_bytes, ZARC_GPU_PX_CHECK_FRAMES and ZARC_GPU_E_CHECK were added WITHOUT a new
                                   version (they are new symbols and new ids; nothing older changed): a library from before them fails a caller
-                                  that wants them at the symbol lookup, not by version */
+                                  that wants them at the symbol lookup, not by version.  zarc_gpu_repack_batch* joined them the same way, for the
+                                  same reason */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -246,6 +250,37 @@ int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 int zarc_gpu_verify_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off,
                                  const uint64_t *frame_len, const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */,
                                  uint8_t *digest /* n*32 */, int *status);
+
+/* ---- repack: one archive's frames into another's, without the content leaving the device ---------------------- */
+/* Decoder::read_content_frame joined to Encoder::add_data_frame: every frame is decoded and judged as zarc_gpu_verify_batch does it, and
+ * what decoded well is encoded again with the handle's CURRENT parameters, out of the scratch it was decoded into.
+ *   - status[i] and digest[i] are EXACTLY what zarc_gpu_verify_batch gives for the same frame and `expect`.  status is required:
+ *     dst_len[i] == 0 alone cannot tell an empty result from a refused frame.
+ *   - A frame whose status is ZARC_GPU_FRAME_OK is re-encoded: level, checksum flag, window log, min match, enable_compression and
+ *     ZARC_GPU_PX_BLOCK_SPLIT are the handle's.  The new frame at dst + dst_off[i], dst_len[i] bytes, is exactly what
+ *     zarc_gpu_pack_batch_device writes for the decoded content.
+ *   - Every other status -- ZARC_GPU_FRAME_CHECKSUM and ZARC_GPU_FRAME_DIGEST included: content that does not match its address is
+ *     never given a new frame -- yields no frame and dst_len[i] = 0.  Its neighbours are unaffected and the call returns ZARC_GPU_OK,
+ *     as unpack does.
+ *   - dst_off[] are slot starts as in pack; slot i has zarc_gpu_bound(raw_len[i]) bytes; dst_cap below their sum: ZARC_GPU_E_DSTSIZE.
+ *     A frame or raw length of 4 GiB or more: ZARC_GPU_E_UNSUPPORTED, checked before any arithmetic.
+ *   - ZARC_GPU_PX_CHECK_FRAMES = 1 applies: the new frames are decoded again and compared with the decoded content they were made
+ *     from; a failure returns ZARC_GPU_E_CHECK as in pack.
+ *   - Neither hash is computed twice: the digest is the decode half's, and the checksum trailer of a new frame is the XXH64 the decoder
+ *     computed of what it decoded (it hashes every frame, whether or not the old frame stored a checksum).
+ *   - Decoded bytes, decoder scratch and encoder scratch are live together and count together against ZARC_GPU_PX_SCRATCH_MB; a batch
+ *     beyond it runs in parts (a single frame alone), with identical results.
+ *   - The host form moves the frames host-to-device (sum of frame_len) and the new frames device-to-host (sum of dst_len), and nothing
+ *     else of content: zarc_gpu_last_copy_bytes reports exactly these sums, the device form 0.
+ *   - zarc_gpu_last_kernel_ms afterwards: T_DECODE, T_DEC_*, T_BLAKE3 and T_XXH64 hold the decode half's times, T_MATCH, T_ENTROPY and
+ *     T_ASSEMBLE the encode half's, T_TOTAL the sum of both halves. */
+int zarc_gpu_repack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                          const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, void *dst, size_t dst_cap, size_t *dst_off, size_t *dst_len,
+                          uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status);
+/* d_frames_base / d_dst are device pointers (frame_off[] need no alignment; d_dst 16-byte aligned), everything else host arrays */
+int zarc_gpu_repack_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                 const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, void *d_dst, size_t dst_cap,
+                                 uint64_t *dst_off, uint64_t *dst_len, uint8_t *digest /* n*32 */, int *status);
 
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,

@@ -38,7 +38,7 @@ EXPORTS = [
     "zarc_gpu_abi_version", "zarc_gpu_level_finder", "zarc_gpu_parameter_advisory", "zarc_gpu_device_count", "zarc_gpu_create", "zarc_gpu_destroy", "zarc_gpu_set_parameter", "zarc_gpu_get_params",
     "zarc_gpu_enable_compression", "zarc_gpu_bound", "zarc_gpu_error_name", "zarc_gpu_frame_status_name", "zarc_gpu_last_error",
     "zarc_gpu_pack_batch", "zarc_gpu_pack_batch_device", "zarc_gpu_pack_batch_dedup", "zarc_gpu_pack_batch_device_dedup", "zarc_gpu_unpack_batch", "zarc_gpu_unpack_batch_device",
-    "zarc_gpu_verify_batch", "zarc_gpu_verify_batch_device", "zarc_gpu_last_copy_bytes",
+    "zarc_gpu_verify_batch", "zarc_gpu_verify_batch_device", "zarc_gpu_last_copy_bytes", "zarc_gpu_repack_batch", "zarc_gpu_repack_batch_device",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -99,6 +99,8 @@ def load(path=None):
     lib.zarc_gpu_unpack_batch_device.argtypes = [vp, sz, vp, u64p, u64p, vp, u64p, u64p, vp, vp, ip]
     lib.zarc_gpu_verify_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vp, ip]
     lib.zarc_gpu_verify_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, ip]
+    lib.zarc_gpu_repack_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vp, sz, szp, szp, vp, ip]
+    lib.zarc_gpu_repack_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, sz, u64p, u64p, vp, ip]
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

@@ -109,6 +109,11 @@ struct zarc_gpu {
     size_t chk_index = 0;       // the first entry that failed the check in the most recent pack pass, and where (ZARC_CHECK_TRAILER: its trailer)
     uint32_t chk_at = 0;
     float chk_ms = 0;           // zarc_check_compare of the most recent pack pass (diagnostic build prints it)
+    // repack (zarc_gpu_repack_batch*): the decode half leaves its bytes in d_vout and the encode half reads them there
+    DevBuf d_vout2;             // read-back check inside a repack pass: d_vout holds the sources, the check decodes into this one
+    DevBuf d_rp_order, d_rp_xxh; // zarc_repack_plan: the caller's index of every frame of the decoder's order; XXH64 by entry for frame assembly
+    bool vout_busy = false;     // a repack pass is between its halves: d_vout is not the check's to take
+    uint64_t dec_scratch = 0;   // decoder scratch (sequences, literals, tables) of the most recent decode, as counted against the budget
     // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
     std::atomic<uint64_t> copy_bytes[ZARC_GPU_C_COUNT] = {};
     bool nested = false;        // a host-pointer entry point is running: the device forms it calls leave the counters alone
@@ -239,6 +244,13 @@ inline std::vector<uint32_t> order_for_decode(const uint64_t *raw_len, const uin
     return order;
 }
 
+// encoder scratch: the slot size a sub-batch whose largest frame has first_len bytes works with, and what one block slot of it costs
+inline uint32_t enc_slot_of(uint64_t first_len) { return (uint32_t)std::min<uint64_t>(ZARC_BLOCK, std::max<uint64_t>((first_len + 15) / 16 * 16, 1024)); }
+inline size_t enc_per_block(bool split, uint32_t slot)
+{
+    const size_t records = (sizeof(ZgeBlock) + sizeof(ZgePlan)) * (split ? 1 + ZGE_SPLIT_K : 1) + (split ? sizeof(ZgePiece) * ZGE_SPLIT_K : 0);
+    return (size_t)(zge_seq_stride(slot) * 8 + zge_lit_stride(slot) + zge_out_stride(slot)) + records;
+}
 inline uint64_t chunks_of(uint64_t len) { return len == 0 ? 1 : (len + 1023) / 1024; }
 inline uint64_t blocks_of(uint64_t len) { return len == 0 ? 1 : (len + ZARC_BLOCK - 1) / ZARC_BLOCK; }
 
@@ -422,7 +434,7 @@ void zarc_gpu_destroy(zarc_gpu_t *h)
     if (h->ev_join3) (void)hipEventDestroy(h->ev_join3);
     for (int i = 0; i < zarc_gpu::PIN_SLOTS; i++) { if (h->pin[i]) (void)hipHostFree(h->pin[i]); if (h->pin_ev[i]) (void)hipEventDestroy(h->pin_ev[i]); }
     h->d_dense.release(); h->d_goff.release(); h->d_glen.release(); h->d_gdense.release();
-    h->d_vout.release(); h->d_chk_off.release(); h->d_chk_order.release(); h->d_chk_slices.release(); h->d_chk_bad.release();
+    h->d_vout.release(); h->d_vout2.release(); h->d_rp_order.release(); h->d_rp_xxh.release(); h->d_chk_off.release(); h->d_chk_order.release(); h->d_chk_slices.release(); h->d_chk_bad.release();
     if (h->meta_pin) (void)hipHostFree(h->meta_pin);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -596,22 +608,33 @@ struct PackCheck {
     uint32_t entry0;           // the decoder's frame 0 is this entry of the pack pass (parts of a split batch)
     uint32_t *first_bad;       // host, by entry from entry0 on: ZARC_CHECK_CLEAN, a byte offset, or ZARC_CHECK_TRAILER
     float *ms;                 // += device time of zarc_check_compare
+    const uint32_t *entry_map; // host, or null: the decoder's frame j is entry entry_map[j] of the pack pass (a pass with skipped entries; entry0 is 0)
+    const uint64_t *xxh;       // device, by entry, or null = h->d_xxh: where the pack pass took its checksums from
+};
+// A pack pass whose per-entry arrays were made on the device (zarc_repack_plan): h->d_off / h->d_len are in place, digests and checksums
+// exist already.  No hash kernel runs; entries whose status is not OK are left out of the size order, so no launch sees them.
+struct PackPlanned {
+    const uint64_t *d_xxh;     // device, by entry: XXH64 of every entry, for frame assembly and the read-back check
+    int *status;               // host, by entry: only ZARC_GPU_FRAME_OK entries are packed; the read-back check marks its failures here
+    size_t budget;             // encoder scratch budget of this pass (0 = the handle's)
 };
 
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, void *d_dst_base,
                         const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk);
 int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, uint64_t *dst_len,
-               int *status, bool trailer);
+               int *status, bool trailer, const PackPlanned *pl = nullptr);
 void check_message(zarc_gpu_t *h, size_t index);
 
 // have_digests: the caller has hashed the entries already (hash-first dedup): no digest kernels, `digest` is not written
+// pl (repack): see PackPlanned; src_off is not looked at (the offsets are on the device), `status` is left alone
 int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_off, const uint64_t *src_len, void *d_dst,
-                     size_t dst_cap, uint64_t *dst_off, uint64_t *dst_len, uint8_t *digest, int *status, bool have_digests)
+                     size_t dst_cap, uint64_t *dst_off, uint64_t *dst_len, uint8_t *digest, int *status, bool have_digests,
+                     const PackPlanned *pl = nullptr)
 {
     int rc = check_common(h, n);
     if (rc) return rc;
     if (n == 0) return ZARC_GPU_OK;
-    if (!d_src_base || !src_off || !src_len || !d_dst || !dst_off || !dst_len || (!digest && !have_digests)) return ZARC_GPU_E_PARAM;
+    if (!d_src_base || (!src_off && !pl) || !src_len || !d_dst || !dst_off || !dst_len || (!digest && !have_digests)) return ZARC_GPU_E_PARAM;
     ZgeParams P = derive_params(h->params); // (slot_bytes is set per sub-batch below)
 #ifdef ZARC_GPU_DIAG
     // host-side phase clock of this call (ZARC_GPU_DBG & 512): where a call over a million entries spends its time outside the kernels
@@ -633,14 +656,16 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
         P.far_back != 48 || P.far_skip != (dp ? 0 : 64) || (fp && P.lazy)) { set_error(h, "internal: encoder parameters differ from the compiled-in ones"); return ZARC_GPU_E_PARAM; }
     uint64_t need = 0;
     for (size_t i = 0; i < n; i++) {
-        if (src_off[i] % ZARC_GPU_ALIGN) { set_error(h, "entry offset not 16-byte aligned"); return ZARC_GPU_E_PARAM; }
+        if (!pl && src_off[i] % ZARC_GPU_ALIGN) { set_error(h, "entry offset not 16-byte aligned"); return ZARC_GPU_E_PARAM; }
         if (src_len[i] >= 0xFFFFFFF0ull) { set_error(h, "entries of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
         dst_off[i] = need;
         need += zarc_gpu_bound((size_t)src_len[i]);
     }
     if (need > dst_cap) return ZARC_GPU_E_DSTSIZE;
-    if ((rc = upload_u64(h, h->d_off, src_off, n))) return rc;
-    if ((rc = upload_u64(h, h->d_len, src_len, n))) return rc;
+    if (!pl) {
+        if ((rc = upload_u64(h, h->d_off, src_off, n))) return rc;
+        if ((rc = upload_u64(h, h->d_len, src_len, n))) return rc;
+    }
     if ((rc = upload_u64(h, h->d_dst_off, dst_off, n))) return rc;
     ZHIP(h->d_dst_len.reserve(n * 8));
     const uint8_t *base = (const uint8_t *)d_src_base;
@@ -648,7 +673,7 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
     Timer t{h};
     int e0, e1, e2;
     ZHIP(t.mark(&e0));
-    if (h->params.compress) {
+    if (h->params.compress && !pl) {
         // the frame checksum is a chain of 64-bit multiplies per entry (few waves, latency-bound): it runs on a side stream from the
         // start and is only waited for by the first frame assembly
         ZHIP(hipEventRecord(h->ev_fork, h->stream));
@@ -679,22 +704,23 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
         h->ms[ZARC_GPU_T_ENTROPY] = 0;
         h->ms[ZARC_GPU_T_ASSEMBLE] = elapsed(h, e1, e2);
         h->ms[ZARC_GPU_T_TOTAL] = h->ms[ZARC_GPU_T_BLAKE3] + h->ms[ZARC_GPU_T_ASSEMBLE];
-        if (h->check_frames) return check_pack(h, n, d_src_base, src_len, d_dst, dst_off, dst_len, status, /*trailer=*/false);
+        if (h->check_frames) return check_pack(h, n, d_src_base, src_len, d_dst, dst_off, dst_len, pl ? pl->status : status, /*trailer=*/false, pl);
         return ZARC_GPU_OK;
     }
     ZHIP(t.mark(&e2));
-    bool xxh_joined = false;
+    bool xxh_joined = pl != nullptr; // (nothing was forked)
 
     // ---- encoder: frames sorted by size (largest first), processed in sub-batches that fit the scratch budget ----
     HOST_PHASE(0); // checks, descriptor uploads, checksum + digest set-up
-    const std::vector<uint32_t> order = order_by_size_desc(src_len, n);
+    std::vector<uint32_t> order = order_by_size_desc(src_len, n);
+    if (pl) order.erase(std::remove_if(order.begin(), order.end(), [pl](uint32_t e) { return pl->status[e] != ZARC_GPU_FRAME_OK; }), order.end());
+    const size_t n_ord = order.size(); // entries that get a frame (all of them unless the pass is a planned one)
     HOST_PHASE(1); // size ordering
     const bool split = h->block_split != 0; // blocks cut where their statistics change (zge_split.hip): ZGE_SPLIT_K piece slots per block
-    const size_t per_block_records = (sizeof(ZgeBlock) + sizeof(ZgePlan)) * (split ? 1 + ZGE_SPLIT_K : 1) + (split ? sizeof(ZgePiece) * ZGE_SPLIT_K : 0);
-    auto per_block_of = [per_block_records](uint32_t slot) { return (size_t)(zge_seq_stride(slot) * 8 + zge_lit_stride(slot) + zge_out_stride(slot)) + per_block_records; };
+    auto per_block_of = [split](uint32_t slot) { return enc_per_block(split, slot); };
     ZHIP(h->d_enc_err.reserve(16));
     ZHIP(hipMemsetAsync(h->d_enc_err.p, 0, 4, h->stream));
-    size_t budget = h->scratch_budget;
+    size_t budget = pl && pl->budget ? pl->budget : h->scratch_budget;
     if (!budget) {
         // up to 64 GiB of scratch (BASELINE configs[1] needs 46 GiB to run as ONE launch per kernel), at most 45 % of what is free
         size_t free_b = 0, total_b = 0;
@@ -705,16 +731,16 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
     float ms_match = 0, ms_ent = 0, ms_asm = 0;
     size_t start = 0;
     std::vector<uint64_t> bp;
-    while (start < n) {
+    while (start < n_ord) {
         // Scratch slots are sized by the largest block of the sub-batch (frames come in descending size): slot_bytes.  A sub-batch also
         // ends where the frames have become four times smaller than its slots, so that a batch of a few large and a million small
         // entries does not give every small one a large slot.
         const uint64_t first_len = src_len[order[start]];
-        const uint32_t slot = (uint32_t)std::min<uint64_t>(ZARC_BLOCK, std::max<uint64_t>(align_up((size_t)first_len, 16), 1024));
+        const uint32_t slot = enc_slot_of(first_len);
         P.slot_bytes = (int)slot;
         const size_t max_blocks = std::max<size_t>(budget / per_block_of(slot), 1);
         size_t end = start, nb = 0;
-        while (end < n) {
+        while (end < n_ord) {
             const size_t b = (size_t)blocks_of(src_len[order[end]]);
             if (end > start && nb + b > max_blocks) break;
             if (end > start + 4096 && slot > 1024 && src_len[order[end]] * 4 <= slot) break;
@@ -850,13 +876,14 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
         ZHIP(hipGetLastError());
         ZHIP(t.mark(&c));
         if (!xxh_joined) { ZHIP(hipStreamWaitEvent(h->stream, h->ev_join, 0)); xxh_joined = true; }
+        const uint64_t *const d_xxh = pl ? pl->d_xxh : h->d_xxh.as<uint64_t>();
         if (split)
             hipLaunchKernelGGL(zarc_zge_assemble_split, dim3((unsigned)m), dim3(256), 0, h->stream, P, base, d_off, d_len, h->d_order.as<uint32_t>(), (uint32_t)m,
-                               h->d_block_prefix.as<uint64_t>(), h->d_blocks.as<ZgeBlock>(), h->d_out.as<uint8_t>(), h->d_xxh.as<uint64_t>(),
+                               h->d_block_prefix.as<uint64_t>(), h->d_blocks.as<ZgeBlock>(), h->d_out.as<uint8_t>(), d_xxh,
                                (uint8_t *)d_dst, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>(), h->d_pblocks.as<ZgeBlock>(), h->d_zpieces.as<ZgePiece>());
         else
             hipLaunchKernelGGL(zarc_zge_assemble, dim3((unsigned)m), dim3(256), 0, h->stream, P, base, d_off, d_len, h->d_order.as<uint32_t>(), (uint32_t)m,
-                               h->d_block_prefix.as<uint64_t>(), h->d_blocks.as<ZgeBlock>(), h->d_out.as<uint8_t>(), h->d_xxh.as<uint64_t>(),
+                               h->d_block_prefix.as<uint64_t>(), h->d_blocks.as<ZgeBlock>(), h->d_out.as<uint8_t>(), d_xxh,
                                (uint8_t *)d_dst, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>());
         ZHIP(hipGetLastError());
         ZHIP(t.mark(&d));
@@ -897,27 +924,28 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
 #endif
     if (have_digests) h->ms[ZARC_GPU_T_BLAKE3] = 0;
     else { float ms = -1.f; if (hipEventElapsedTime(&ms, h->ev_b3[0], h->ev_b3[1]) == hipSuccess) h->ms[ZARC_GPU_T_BLAKE3] = ms; } // side stream: queue wait + kernels
-    h->ms[ZARC_GPU_T_XXH64] = elapsed(h, 14, 15); // side stream: overlaps the match finder, not part of the total
+    h->ms[ZARC_GPU_T_XXH64] = pl ? 0 : elapsed(h, 14, 15); // side stream: overlaps the match finder, not part of the total
     h->ms[ZARC_GPU_T_MATCH] = ms_match;
     h->ms[ZARC_GPU_T_ENTROPY] = ms_ent;
     h->ms[ZARC_GPU_T_ASSEMBLE] = ms_asm;
     h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e1) + ms_match + ms_ent + ms_asm; // the digest and the checksum run beside these
     // read-back check: pack has taken its results off the buffers it shares with the decoder; sources and frames are still resident
-    if (h->check_frames) return check_pack(h, n, d_src_base, src_len, d_dst, dst_off, dst_len, status, P.checksum != 0);
+    if (h->check_frames) return check_pack(h, n, d_src_base, src_len, d_dst, dst_off, dst_len, pl ? pl->status : status, P.checksum != 0, pl);
     return ZARC_GPU_OK;
 }
 
 // ZARC_GPU_PX_CHECK_FRAMES: decode the frames this pass has assembled (decode-only, into the handle's scratch) and compare the bytes with
 // the sources (zarc_check_compare).  The decoder's timers stay out of h->ms: the call reports pack's.
+// pl (repack): only the entries the pass has packed (status OK) have a frame to check
 int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, uint64_t *dst_len,
-               int *status, bool trailer)
+               int *status, bool trailer, const PackPlanned *pl)
 {
 #ifdef ZARC_GPU_DIAG
     // fault injection (diagnostic build only): one byte of one assembled frame, between assembly and the check.  The decoder is built to
     // distrust what it reads; this shows the check failing, which it otherwise never would
     for (int tail = 0; tail < 2; tail++) {
         const int idx = diag_env(tail ? "ZARC_GPU_CHECK_FLIP_TAIL" : "ZARC_GPU_CHECK_FLIP_BODY", -1);
-        if (idx < 0 || (size_t)idx >= n || dst_len[idx] == 0) continue;
+        if (idx < 0 || (size_t)idx >= n || (pl && pl->status[idx] != ZARC_GPU_FRAME_OK) || dst_len[idx] == 0) continue;
         uint8_t *at = (uint8_t *)d_dst + dst_off[idx] + (tail ? dst_len[idx] - 1 : dst_len[idx] / 2), v = 0;
         ZHIP(hipMemcpy(&v, at, 1, hipMemcpyDeviceToHost));
         v ^= 0xFF;
@@ -926,8 +954,21 @@ int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *
 #endif
     std::vector<uint32_t> first_bad(n, ZARC_CHECK_CLEAN);
     h->chk_ms = 0;
-    const PackCheck chk{(const uint8_t *)d_src_base, trailer, 0u, first_bad.data(), &h->chk_ms};
-    const int rc = unpack_device_split(h, n, d_dst, dst_off, dst_len, nullptr, nullptr, src_len, nullptr, nullptr, nullptr, &chk);
+    int rc;
+    if (pl) {
+        std::vector<uint32_t> keep, bad;
+        std::vector<uint64_t> off, len, raw;
+        for (size_t i = 0; i < n; i++)
+            if (pl->status[i] == ZARC_GPU_FRAME_OK) { keep.push_back((uint32_t)i); off.push_back(dst_off[i]); len.push_back(dst_len[i]); raw.push_back(src_len[i]); }
+        if (keep.empty()) return ZARC_GPU_OK;
+        bad.assign(keep.size(), ZARC_CHECK_CLEAN);
+        const PackCheck chk{(const uint8_t *)d_src_base, trailer, 0u, bad.data(), &h->chk_ms, keep.data(), pl->d_xxh};
+        rc = unpack_device_split(h, keep.size(), d_dst, off.data(), len.data(), nullptr, nullptr, raw.data(), nullptr, nullptr, nullptr, &chk);
+        for (size_t j = 0; j < keep.size(); j++) first_bad[keep[j]] = bad[j];
+    } else {
+        const PackCheck chk{(const uint8_t *)d_src_base, trailer, 0u, first_bad.data(), &h->chk_ms, nullptr, nullptr};
+        rc = unpack_device_split(h, n, d_dst, dst_off, dst_len, nullptr, nullptr, src_len, nullptr, nullptr, nullptr, &chk);
+    }
     if (rc) return rc;
 #ifdef ZARC_GPU_DIAG
     if (diag_env("ZARC_GPU_CHECK_STATS", 0)) fprintf(stderr, "zarc_check_compare: %.3f ms\n", h->chk_ms);
@@ -1013,9 +1054,10 @@ constexpr int UNPACK_SPLIT = -1000; // internal: the decoder's scratch for this 
 // own_out: bytes of engine-owned output scratch this call decodes into (verify, read-back check); they count against the budget
 int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off_in, const uint64_t *frame_len_in,
                        void *d_dst_base, const uint64_t *dst_off_in, const uint64_t *raw_len_in, const uint8_t *expect_in, uint8_t *digest,
-                       int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr)
+                       int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr, DevBuf *order_out = nullptr)
 {
     int rc = 0;
+    h->dec_scratch = 0;
     DevBuf &b_dst_off = chk ? h->d_chk_off : h->d_dst_off;
     uint64_t total_raw = 0;
     for (size_t i = 0; i < n; i++) {
@@ -1036,6 +1078,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if ((rc = upload_u64(h, b_dst_off, dst_off.data(), n))) return rc;
     if ((rc = upload_u64(h, h->d_raw_len, raw_len.data(), n))) return rc;
     { std::vector<uint32_t> ident(n); std::iota(ident.begin(), ident.end(), 0u); if ((rc = upload_u32(h, h->d_order, ident.data(), n))) return rc; } // the queues walk the (sorted) indices
+    if (order_out && (rc = upload_u32(h, *order_out, order.data(), n))) return rc; // repack: zarc_repack_plan takes the results back to the caller's order
     const size_t dec_grid = std::min<size_t>(n, (size_t)h->num_cus * 16); // 4 waves per SIMD (launch bounds of the frame kernels: 128 VGPRs, no spills)
     ZHIP(h->d_declit.reserve(dec_grid * (size_t)(ZARC_BLOCK_MAX + 64)));
     ZHIP(h->d_queue.reserve(256));
@@ -1179,7 +1222,8 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
             seqidx[nslots] = total; litidx[nslots] = lit_total;
             total_seqs = total; total_lits = lit_total;
         }
-        if (h->scratch_budget && n > 1 && own_out + total_seqs * 8 + total_lits + nslots * (uint64_t)(ZDEC_TABLE_CELLS * 2 + sizeof(ZdecBlock) + 32) > h->scratch_budget) return UNPACK_SPLIT;
+        h->dec_scratch = total_seqs * 8 + total_lits + nslots * (uint64_t)(ZDEC_TABLE_CELLS * 2 + sizeof(ZdecBlock) + 32);
+        if (h->scratch_budget && n > 1 && own_out + h->dec_scratch > h->scratch_budget) return UNPACK_SPLIT;
         if (!lean) {
             if ((rc = upload_u64(h, h->d_seqidx, seqidx.data(), nslots))) return rc;
             if ((rc = upload_u64(h, h->d_litidx, litidx.data(), nslots))) return rc;
@@ -1411,14 +1455,18 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         for (size_t i = 0; i < n; i++) slices[i + 1] = slices[i] + std::max<uint64_t>(1, (raw_len[i] + ZARC_CHECK_SLICE - 1) / ZARC_CHECK_SLICE);
         if (slices[n] > 0x7FFFFFFFull) { set_error(h, "read-back check: batch too large"); return ZARC_GPU_E_PARAM; }
         if ((rc = upload_u64(h, h->d_chk_slices, slices.data(), n + 1))) return rc;
-        if ((rc = upload_u32(h, h->d_chk_order, order.data(), n))) return rc;
+        if (chk->entry_map) { // a pass with skipped entries: the frames are a subset of its entries
+            std::vector<uint32_t> mapped(n);
+            for (size_t i = 0; i < n; i++) mapped[i] = chk->entry_map[order[i]];
+            if ((rc = upload_u32(h, h->d_chk_order, mapped.data(), n))) return rc;
+        } else if ((rc = upload_u32(h, h->d_chk_order, order.data(), n))) return rc;
         ZHIP(h->d_chk_bad.reserve(n * 4));
         ZHIP(hipMemsetAsync(h->d_chk_bad.p, 0xFF, n * 4, h->stream));
         ZHIP(t.mark(&e3));
         hipLaunchKernelGGL(zarc_check_compare, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_chk_slices.as<uint64_t>(), h->d_chk_order.as<uint32_t>(),
                            chk->entry0, (const uint8_t *)d_dst_base, b_dst_off.as<uint64_t>(), h->d_status.as<int32_t>(), chk->src_base, h->d_off.as<uint64_t>(),
                            h->d_len.as<uint64_t>(), (const uint8_t *)d_frames_base, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>(),
-                           chk->trailer ? h->d_xxh.as<uint64_t>() : (const uint64_t *)nullptr, h->d_chk_bad.as<uint32_t>());
+                           chk->trailer ? (chk->xxh ? chk->xxh : h->d_xxh.as<uint64_t>()) : (const uint64_t *)nullptr, h->d_chk_bad.as<uint32_t>());
         ZHIP(hipGetLastError());
         int e4;
         ZHIP(t.mark(&e4));
@@ -1494,6 +1542,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
                         const PackCheck *chk = nullptr)
 {
     const bool own = d_dst_base == nullptr;
+    DevBuf &vout = h->vout_busy ? h->d_vout2 : h->d_vout; // (the read-back check inside a repack pass: d_vout holds what it compares with)
     uint64_t total = 0, acc = 0, own_bytes = 0;
     for (size_t i = 0; i < n; i++) { total += raw_len[i]; own_bytes += (raw_len[i] + (ZARC_GPU_ALIGN - 1)) & ~(uint64_t)(ZARC_GPU_ALIGN - 1); }
     if (!own) own_bytes = 0;
@@ -1502,18 +1551,18 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
     if (own && attempt) {
         if (n >= 2 && h->scratch_budget && own_bytes > h->scratch_budget) attempt = false;
         else {
-            const hipError_t e = h->d_vout.reserve(own_bytes + ZARC_GPU_PAD + 256);
+            const hipError_t e = vout.reserve(own_bytes + ZARC_GPU_PAD + 256);
             if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); rc = ZARC_GPU_E_NOMEM; attempt = false; }
             else ZHIP(e);
         }
     }
     if (attempt)
-        rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, own ? h->d_vout.p : d_dst_base, own ? nullptr : dst_off, raw_len, expect, digest,
+        rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, own ? vout.p : d_dst_base, own ? nullptr : dst_off, raw_len, expect, digest,
                                 status, own_bytes, chk);
     if ((rc != UNPACK_SPLIT && rc != ZARC_GPU_E_NOMEM) || n < 2) return rc == UNPACK_SPLIT ? ZARC_GPU_E_NOMEM : rc;
     (void)hipStreamSynchronize(h->stream);
     if (rc == ZARC_GPU_E_NOMEM) {
-        DevBuf *big[] = {&h->d_seqs, &h->d_lits, &h->d_ztables, &h->d_zblocks, &h->d_seqidx, &h->d_litidx, &h->d_nseq, &h->d_vout};
+        DevBuf *big[] = {&h->d_seqs, &h->d_lits, &h->d_ztables, &h->d_zblocks, &h->d_seqidx, &h->d_litidx, &h->d_nseq, &vout};
         for (DevBuf *b : big) b->release();
         if (!chk) { h->d_cvs.release(); h->d_cvs_tmp.release(); }
         if (!h->dec_split_above || total < h->dec_split_above) h->dec_split_above = total;
@@ -1527,7 +1576,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
     for (int p = 0; p < 2; p++) {
         const size_t a = part[p], m = part[p + 1] - a;
         PackCheck sub{};
-        if (chk) { sub = *chk; sub.entry0 += (uint32_t)a; sub.first_bad += a; }
+        if (chk) { sub = *chk; sub.first_bad += a; if (chk->entry_map) sub.entry_map += a; else sub.entry0 += (uint32_t)a; }
         rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
                                  digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr);
         if (rc) return rc;
@@ -1559,6 +1608,128 @@ int zarc_gpu_verify_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_b
     if (n == 0) return ZARC_GPU_OK;
     if (!d_frames_base || !frame_off || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
     return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status);
+}
+
+
+// ---- repack: Decoder::read_content_frame joined to Encoder::add_data_frame without the bytes leaving HBM --------------------------
+// One pass = the decode half of verify (unpack_device_once into d_vout: the same decoder, hash passes and verdict), zarc_repack_plan, the
+// encode half (pack_device_impl over d_vout, planned: no hash kernel runs, entries without an OK verdict are in no launch).  d_vout is laid
+// out by the decoder -- 16-byte aligned entries, ZARC_GPU_PAD and more readable behind the last -- which is what pack asks of an arena.
+} // extern "C"
+namespace {
+// encoder scratch a pass needs at the very least: its largest frame packed alone (store mode: none)
+uint64_t enc_scratch_min(const zarc_gpu *h, uint64_t max_len)
+{
+    return h->params.compress ? (uint64_t)enc_per_block(h->block_split != 0, enc_slot_of(max_len)) * blocks_of(max_len) : 0;
+}
+
+int repack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, const uint64_t *raw_len,
+                       const uint8_t *expect, uint8_t *d_slots, size_t slots_cap, uint64_t *dst_off, uint64_t *dst_len, uint8_t *digest, int *status,
+                       uint64_t own_bytes, uint64_t enc_min)
+{
+    // what the plan kernel writes is reserved in front of the decode half: nothing is reallocated between that kernel and its readers
+    ZHIP(h->d_off.reserve(n * 8));
+    ZHIP(h->d_len.reserve(n * 8));
+    ZHIP(h->d_rp_xxh.reserve(n * 8));
+    int rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, h->d_vout.p, nullptr, raw_len, expect, digest, status, own_bytes + enc_min, nullptr,
+                                &h->d_rp_order);
+    if (rc) return rc;
+    float dec_ms[ZARC_GPU_T_COUNT];
+    for (int t = 0; t < ZARC_GPU_T_COUNT; t++) dec_ms[t] = h->ms[t];
+    // the decoder's arrays (its own order) -> pack's (the caller's order).  The decoder hashes every frame it decodes, with or without a
+    // stored checksum, so the XXH64 of every good entry exists: the encode half computes none
+    hipLaunchKernelGGL(zarc_repack_plan, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, (uint32_t)n, h->d_rp_order.as<uint32_t>(), h->d_status.as<int32_t>(),
+                       h->d_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_xxh.as<uint64_t>(), h->d_off.as<uint64_t>(), h->d_len.as<uint64_t>(),
+                       h->d_rp_xxh.as<uint64_t>());
+    ZHIP(hipGetLastError());
+    // decoded bytes and decoder scratch stay live beside the encoder's scratch: it gets what they leave of the budget, and never less than
+    // its largest frame needs (repack_device_split has halved the batch for that where it could)
+    size_t enc_budget = 0;
+    if (h->scratch_budget) {
+        const uint64_t used = own_bytes + h->dec_scratch;
+        enc_budget = (size_t)std::max<uint64_t>(std::max<uint64_t>(enc_min, 1), h->scratch_budget > used ? h->scratch_budget - used : 0);
+    }
+    const PackPlanned pl{h->d_rp_xxh.as<uint64_t>(), status, enc_budget};
+    h->vout_busy = true;
+    rc = pack_device_impl(h, n, h->d_vout.p, nullptr, raw_len, d_slots, slots_cap, dst_off, dst_len, nullptr, nullptr, /*have_digests=*/true, &pl);
+    h->vout_busy = false;
+    if (rc && rc != ZARC_GPU_E_CHECK) return rc;
+    for (size_t i = 0; i < n; i++) if (status[i] != ZARC_GPU_FRAME_OK) dst_len[i] = 0; // no frame (a store-mode pass has written an empty one into the slot)
+    const float enc_total = h->ms[ZARC_GPU_T_TOTAL];
+    for (int t : {ZARC_GPU_T_BLAKE3, ZARC_GPU_T_XXH64, ZARC_GPU_T_DECODE, ZARC_GPU_T_DEC_SEQS, ZARC_GPU_T_DEC_LITS, ZARC_GPU_T_DEC_FRAMES}) h->ms[t] = dec_ms[t];
+    h->ms[ZARC_GPU_T_TOTAL] = dec_ms[ZARC_GPU_T_TOTAL] + enc_total;
+    return rc;
+}
+
+// A pass that does not fit -- the budget of ZARC_GPU_PX_SCRATCH_MB or the device -- runs as two, each of which may split again, the way
+// unpack_device_split treats verify: halved before it is tried when decoded bytes plus the least encoder scratch exceed the budget, after
+// the decoder's sizing kernels when its scratch does not fit either, after an allocation failure.  A single frame runs alone.  Frames are
+// independent on both sides, so the output is the same for every budget.  slot_base: where this part's slots start in d_dst.
+int repack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, const uint64_t *raw_len,
+                        const uint8_t *expect, uint8_t *d_dst, uint64_t slot_base, uint64_t *dst_off, uint64_t *dst_len, uint8_t *digest, int *status)
+{
+    uint64_t total = 0, acc = 0, own_bytes = 0, max_len = 0, slots = 0;
+    for (size_t i = 0; i < n; i++) {
+        total += raw_len[i]; own_bytes += align_up((size_t)raw_len[i], ZARC_GPU_ALIGN); max_len = std::max(max_len, raw_len[i]); slots += zarc_gpu_bound((size_t)raw_len[i]);
+    }
+    const uint64_t enc_min = enc_scratch_min(h, max_len);
+    int rc = UNPACK_SPLIT;
+    bool attempt = !(n >= 2 && h->dec_split_above && total >= h->dec_split_above);
+    if (attempt) {
+        if (n >= 2 && h->scratch_budget && own_bytes + enc_min > h->scratch_budget) attempt = false;
+        else {
+            const hipError_t e = h->d_vout.reserve(own_bytes + ZARC_GPU_PAD + 256);
+            if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); rc = ZARC_GPU_E_NOMEM; attempt = false; }
+            else ZHIP(e);
+        }
+    }
+    if (attempt) {
+        rc = repack_device_once(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, d_dst + slot_base, (size_t)slots, dst_off, dst_len, digest, status, own_bytes, enc_min);
+        if (rc == ZARC_GPU_OK || rc == ZARC_GPU_E_CHECK) for (size_t i = 0; i < n; i++) dst_off[i] += slot_base;
+    }
+    if ((rc != UNPACK_SPLIT && rc != ZARC_GPU_E_NOMEM) || n < 2) return rc == UNPACK_SPLIT ? ZARC_GPU_E_NOMEM : rc;
+    (void)hipStreamSynchronize(h->stream);
+    if (rc == ZARC_GPU_E_NOMEM) {
+        DevBuf *big[] = {&h->d_seqs, &h->d_lits, &h->d_ztables, &h->d_zblocks, &h->d_seqidx, &h->d_litidx, &h->d_nseq, &h->d_vout, &h->d_vout2, &h->d_cvs, &h->d_cvs_tmp,
+                         &h->d_seq, &h->d_lit, &h->d_out, &h->d_blocks, &h->d_plan, &h->d_pblocks, &h->d_zpieces};
+        for (DevBuf *b : big) b->release();
+        if (!h->dec_split_above || total < h->dec_split_above) h->dec_split_above = total;
+    }
+    size_t k = 0;
+    while (k + 1 < n && (acc + raw_len[k]) * 2 <= total) acc += raw_len[k++];
+    if (k == 0) k = 1;
+    float ms[ZARC_GPU_T_COUNT];
+    const size_t part[3] = {0, k, n};
+    for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] = 0;
+    for (int p = 0; p < 2; p++) {
+        const size_t a = part[p], m = part[p + 1] - a;
+        rc = repack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, raw_len + a, expect ? expect + a * 32 : nullptr, d_dst, slot_base, dst_off + a,
+                                 dst_len + a, digest + a * 32, status + a);
+        if (rc == ZARC_GPU_E_CHECK) check_message(h, a + h->chk_index);
+        if (rc) return rc;
+        for (size_t i = a; i < a + m; i++) slot_base += zarc_gpu_bound((size_t)raw_len[i]);
+        for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] += h->ms[i] > 0 ? h->ms[i] : 0;
+    }
+    for (int i = 0; i < ZARC_GPU_T_COUNT; i++) h->ms[i] = ms[i];
+    return ZARC_GPU_OK;
+}
+} // namespace
+extern "C" {
+
+int zarc_gpu_repack_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                 const uint64_t *raw_len, const uint8_t *expect, void *d_dst, size_t dst_cap, uint64_t *dst_off, uint64_t *dst_len,
+                                 uint8_t *digest, int *status)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len || !d_dst || !dst_off || !dst_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    for (size_t i = 0; i < n; i++)
+        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; } // before any size arithmetic
+    uint64_t need = 0;
+    for (size_t i = 0; i < n; i++) need += zarc_gpu_bound((size_t)raw_len[i]);
+    if (need > dst_cap) return ZARC_GPU_E_DSTSIZE;
+    return repack_device_split(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, (uint8_t *)d_dst, 0, dst_off, dst_len, digest, status);
 }
 
 // ---- host-memory entry points: stage through engine-owned arenas -----------------------------------
@@ -2016,6 +2187,108 @@ int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
         if (helper_rc) return helper_rc;
         for (int t = 0; t < ZARC_GPU_T_COUNT; t++) sum[t] += h->ms[t] > 0 ? h->ms[t] : 0;
     }
+    for (int t = 0; t < ZARC_GPU_T_COUNT; t++) h->ms[t] = sum[t];
+    return ZARC_GPU_OK;
+}
+
+
+// verify's way in and pack's way out around zarc_gpu_repack_batch_device, per staged chunk: chunk c+1's frames come in and chunk c-1's
+// new frames go out while chunk c is decoded and encoded.  Nothing else of content moves: the decoded bytes stay in the handle's scratch.
+int zarc_gpu_repack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                          const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], void *dst, size_t dst_cap, size_t *dst_off, size_t *dst_len,
+                          uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!frame || !frame_len || !raw_len || !dst || !dst_off || !dst_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    NestedCall nested(h);
+    std::vector<uint64_t> in_sz(n), out_sz(n), weight(n), flen(n), rlen(n);
+    for (size_t i = 0; i < n; i++) {
+        if (frame_len[i] && !frame[i]) return ZARC_GPU_E_PARAM;
+        if ((uint64_t)frame_len[i] >= 0xFFFFFFF0ull || (uint64_t)raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; } // before any size arithmetic or staging
+    }
+    uint64_t need = 0;
+    for (size_t i = 0; i < n; i++) {
+        flen[i] = frame_len[i]; rlen[i] = raw_len[i];
+        in_sz[i] = align_up(frame_len[i], ZARC_GPU_ALIGN);
+        out_sz[i] = zarc_gpu_bound(raw_len[i]);
+        weight[i] = std::max<uint64_t>(in_sz[i], align_up(raw_len[i], ZARC_GPU_ALIGN)); // a chunk is cut by what the kernels work on: the decoded bytes
+        dst_off[i] = (size_t)need; // the caller's buffer uses the same slot layout as the device arena
+        need += out_sz[i];
+    }
+    if (need > dst_cap) return ZARC_GPU_E_DSTSIZE;
+    const std::vector<Chunk> cs = make_chunks(n, in_sz, out_sz, weight, h->stage_chunk ? h->stage_chunk : (uint64_t)2 << 30, /*ramp=*/true); // the encode half is the slow one: pack's chunks
+    uint64_t max_in = 0, max_out = 0;
+    for (const Chunk &c : cs) { max_in = std::max(max_in, c.in_bytes); max_out = std::max(max_out, c.out_bytes); }
+    const uint64_t in_half = align_up(max_in + ZARC_GPU_PAD + 256, 256), out_half = align_up(max_out + ZARC_GPU_PAD, 256);
+    ZHIP(h->d_arena_in.reserve(2 * in_half));
+    ZHIP(h->d_arena_out.reserve(2 * out_half));
+    uint8_t *const ain = h->d_arena_in.as<uint8_t>(), *const aout = h->d_arena_out.as<uint8_t>();
+    const int device = h->device;
+    hipStream_t side = h->stream_stage, side_out = h->stream_stage_out;
+    std::vector<uint64_t> doff(n), dlen(n);
+    auto copy_in = [&](size_t c) -> int {
+        std::vector<Seg> segs;
+        uint64_t at = 0;
+        for (size_t i = cs[c].i0; i < cs[c].i1; i++) { if (frame_len[i]) segs.push_back(Seg{(uint8_t *)frame[i], at, frame_len[i]}); at += in_sz[i]; }
+        return staged_h2d(h, side, segs, ain + (c & 1) * in_half, at);
+    };
+    auto copy_out = [&](size_t c) -> int { // new frames of chunk c (lengths known): packed back to back on the device, then to the caller's slots
+        const size_t m = cs[c].i1 - cs[c].i0, i0 = cs[c].i0;
+        std::vector<uint64_t> dense(m);
+        std::vector<Seg> segs;
+        uint64_t at = 0;
+        for (size_t k = 0; k < m; k++) { dense[k] = at; if (dlen[i0 + k]) segs.push_back(Seg{(uint8_t *)dst + dst_off[i0 + k], at, dlen[i0 + k]}); at += dlen[i0 + k]; }
+        if (h->d_dense.reserve(at + 256) != hipSuccess || h->d_goff.reserve(m * 8) != hipSuccess || h->d_glen.reserve(m * 8) != hipSuccess ||
+            h->d_gdense.reserve(m * 8) != hipSuccess) return ZARC_GPU_E_NOMEM;
+        if (hipMemcpyAsync(h->d_goff.p, doff.data() + i0, m * 8, hipMemcpyHostToDevice, side_out) != hipSuccess ||
+            hipMemcpyAsync(h->d_glen.p, dlen.data() + i0, m * 8, hipMemcpyHostToDevice, side_out) != hipSuccess ||
+            hipMemcpyAsync(h->d_gdense.p, dense.data(), m * 8, hipMemcpyHostToDevice, side_out) != hipSuccess) return ZARC_GPU_E_DEVICE;
+        hipLaunchKernelGGL(zarc_gather, dim3((unsigned)m), dim3(256), 0, side_out, aout + (c & 1) * out_half, h->d_goff.as<uint64_t>(), h->d_glen.as<uint64_t>(),
+                           h->d_gdense.as<uint64_t>(), (uint32_t)m, h->d_dense.as<uint8_t>());
+        if (hipGetLastError() != hipSuccess) return ZARC_GPU_E_DEVICE;
+        const int r = staged_d2h(h, side_out, segs, h->d_dense.as<uint8_t>(), at);
+        if (hipStreamSynchronize(side_out) != hipSuccess) return ZARC_GPU_E_DEVICE; // `dense` is read by an async copy above
+        return r;
+    };
+    float sum[ZARC_GPU_T_COUNT] = {};
+    if ((rc = copy_in(0))) return rc;
+    ZHIP(hipStreamSynchronize(side));
+    for (size_t c = 0; c < cs.size(); c++) {
+        int helper_rc = 0, helper_rc_out = 0;
+        auto move_in = [&] {
+            (void)hipSetDevice(device);
+            if (c + 1 < cs.size()) helper_rc = copy_in(c + 1);
+            if (hipStreamSynchronize(side) != hipSuccess) helper_rc = ZARC_GPU_E_DEVICE;
+        };
+        auto move_out = [&] {
+            (void)hipSetDevice(device);
+            if (c > 0) helper_rc_out = copy_out(c - 1);
+            if (hipStreamSynchronize(side_out) != hipSuccess) helper_rc_out = ZARC_GPU_E_DEVICE;
+        };
+        std::thread helper, helper_out;
+        if (h->stage_thread) { helper = std::thread(move_in); helper_out = std::thread(move_out); } else { move_in(); move_out(); }
+        const size_t m = cs[c].i1 - cs[c].i0, i0 = cs[c].i0;
+        std::vector<uint64_t> foff(m);
+        uint64_t fa = 0;
+        for (size_t k = 0; k < m; k++) { foff[k] = fa; fa += in_sz[i0 + k]; }
+        rc = zarc_gpu_repack_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0, expect ? (const uint8_t *)expect[i0] : nullptr,
+                                          aout + (c & 1) * out_half, cs[c].out_bytes, doff.data() + i0, dlen.data() + i0, (uint8_t *)digest[i0], status + i0);
+        if (helper.joinable()) helper.join();
+        if (helper_out.joinable()) helper_out.join();
+        if (rc == ZARC_GPU_E_CHECK) { // the batch's output is void: say which frame of the batch it was
+            for (size_t k = 0; k < m; k++) dst_len[i0 + k] = (size_t)dlen[i0 + k];
+            check_message(h, i0 + h->chk_index);
+        }
+        if (rc) return rc;
+        if (helper_rc) return helper_rc;
+        if (helper_rc_out) return helper_rc_out;
+        for (size_t k = 0; k < m; k++) dst_len[i0 + k] = (size_t)dlen[i0 + k];
+        for (int t = 0; t < ZARC_GPU_T_COUNT; t++) sum[t] += h->ms[t] > 0 ? h->ms[t] : 0;
+    }
+    if ((rc = copy_out(cs.size() - 1))) return rc;
+    ZHIP(hipStreamSynchronize(side_out));
     for (int t = 0; t < ZARC_GPU_T_COUNT; t++) h->ms[t] = sum[t];
     return ZARC_GPU_OK;
 }

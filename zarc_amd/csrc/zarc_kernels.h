@@ -192,6 +192,10 @@ __global__ void zarc_check_compare(uint32_t n, const uint64_t *slice_prefix, con
                                    const uint64_t *dec_off, const int32_t *dec_status, const uint8_t *src_base, const uint64_t *src_off /* pack */,
                                    const uint64_t *src_len /* pack */, const uint8_t *frame_base, const uint64_t *frame_off /* pack */,
                                    const uint64_t *frame_len /* pack */, const uint64_t *xxh /* pack; null = no trailer to look at */, uint32_t *first_bad);
+// repack (zge_repack.hip): the decode half's per-frame arrays (decoder order) -> the pack pass's per-entry arrays (entry_of[i] = the entry
+// of frame i); a frame whose status is not OK becomes an entry of no bytes
+__global__ void zarc_repack_plan(uint32_t n, const uint32_t *entry_of, const int32_t *status, const uint64_t *dec_off, const uint64_t *raw_len,
+                                 const uint64_t *dec_xxh, uint64_t *src_off /* pack */, uint64_t *src_len /* pack */, uint64_t *xxh /* pack */);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

@@ -140,6 +140,7 @@ __global__ void __launch_bounds__(256) zarc_gather(const uint8_t *__restrict__ s
 }
 
 #include "zge_check.hip" // zarc_check_compare: the read-back check of a pack call
+#include "zge_repack.hip" // zarc_repack_plan: decode half -> encode half of a repack pass
 
 // Store mode (Encoder::enable_compression(false), crates/zarc/src/encode.rs:95-97 -> write_uncompressed_frame,
 // encode/lowlevel_frames.rs:47-84): the content goes into Raw blocks.  Like the reference's frame this one carries an

@@ -155,6 +155,25 @@ class Engine:
             dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return dig, status
 
+    def repack_device(self, d_frames, frame_off, frame_len, raw_len, d_dst, dst_cap, expect=None):
+        """verify_device joined to pack_device: frames with status OK are encoded again with the handle's parameters into d_dst.
+        -> (dst_off, dst_len, digests, statuses)"""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dst_off, dst_len = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        self._check(self.lib.zarc_gpu_repack_batch_device(
+            self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            ctypes.c_void_p(d_dst), dst_cap, dst_off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            dst_len.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return dst_off, dst_len, dig, status
+
     # ---- host-memory batch calls (the shape of the reference's API: slices in, bytes out) ----
     def blake3(self, entries):
         n = len(entries)
@@ -267,3 +286,25 @@ class Engine:
                                                    exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
                                                    dig.ctypes.data_as(ctypes.c_void_p), status))
         return [(bytes(dig[i]), int(status[i])) for i in range(n)]
+
+    def repack(self, frames, raw_lens, expect=None):
+        """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with
+        the handle's current parameters -- the bytes pack() makes of what unpack() delivers -- and every other one gives None.  Only the
+        old frames cross to the device and only the new ones come back."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        cap = sum(self.bound(int(r)) for r in raw_lens)
+        dst = np.zeros(max(cap, 1), dtype=np.uint8)
+        dst_off, dst_len = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        self._check(self.lib.zarc_gpu_repack_batch(self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+                                                   dst.ctypes.data_as(ctypes.c_void_p), cap, dst_off, dst_len, dig.ctypes.data_as(ctypes.c_void_p), status))
+        new = [bytes(dst[dst_off[i]:dst_off[i] + dst_len[i]]) if status[i] == _lib.FRAME_OK else None for i in range(n)]
+        return new, [bytes(d) for d in dig], [int(x) for x in status]

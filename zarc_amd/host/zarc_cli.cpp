@@ -1,4 +1,4 @@
-// zarc_amd/host/zarc_cli.cpp -- `zarc pack | unpack | list-files` over the engine (SURVEY.md section 8 rows f2 + f3).
+// zarc_amd/host/zarc_cli.cpp -- `zarc pack | unpack | verify | repack | list-files` over the engine (SURVEY.md section 8 rows f2 + f3).
 //
 // Same verbs, flags and outputs as the reference CLI (crates/zarc-cli/src/args.rs:17-84):
 //   pack        --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L|--follow-symlinks] PATH...
@@ -6,6 +6,9 @@
 //               -> add_data_frame, entry -> add_file_entry, finalise, prints "digest: <base64>"
 //   unpack      INPUT [--filter REGEX]... [--verify DIGEST]        crates/zarc-cli/src/unpack.rs:18-138
 //   list-files  INPUT [--only-files] [--decorate] [--filter REGEX]...   crates/zarc-cli/src/list_files.rs:8-63
+//   repack      INPUT --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [--split-blocks] [--check] [--gpus N] [--verify DIGEST]
+//               [--keep-smaller]     engine extension (the reference would unpack and pack again): the content frames of INPUT encoded
+//               again with pack's flags, on the device; the directory is carried over
 //   global      -v... (warn / info / debug / trace), --log-file [PATH] (JSON lines; a directory gets zarc.<UTC time>.log), $RUST_LOG
 //               takes precedence -- crates/zarc-cli/src/args.rs:39-65, logs.rs:12-67
 // What differs on purpose: file contents are gathered into batches of about 1 GiB before they go to the engine (frames
@@ -179,7 +182,7 @@ bool safe_name(const std::vector<std::string> &name)
 
 int usage()
 {
-    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|list-files> ...\n"
+    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|list-files> ...\n"
                          "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] [--split-blocks] [--check] PATH...\n"
                          "         --split-blocks  cut 64 KiB blocks where their statistics change (smaller frames on binaries / JSON; off by default)\n"
                          "         --check         decode every frame again on the device and compare it with its file before it is written; a mismatch\n"
@@ -187,6 +190,11 @@ int usage()
                          "       zarc unpack INPUT [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
                          "       zarc verify INPUT [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
                          "         tests the content frames of the files (each distinct frame once) without writing anything; exit status 0 iff all are good\n"
+                         "       zarc repack INPUT --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [--split-blocks] [--check] [--gpus N]\n"
+                         "                   [--verify DIGEST] [--keep-smaller]\n"
+                         "         encodes every content frame of INPUT again with these flags (pack's), on the device, and carries the directory over;\n"
+                         "         --keep-smaller copies a frame unchanged when its new form is not smaller.  A frame that is not good ends the run with\n"
+                         "         exit status 1 and nothing is left at PATH\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -218,6 +226,45 @@ bool parse_zstd_param(const std::string &s, ZstdParam *out) // pack.rs:86-217: N
         }
     return false;
 }
+
+// The flags that say what frames an encoder writes: pack's, and repack's
+struct EncoderFlags {
+    std::vector<ZstdParam> params;
+    bool store = false, have_level = false, split_blocks = false, check = false;
+    int level = 0;
+    // 1: a[i] (and its value, i advanced) was one of these flags; 0: it was not; -1: it was, with a bad value
+    int parse(const std::vector<std::string> &a, size_t &i)
+    {
+        if (a[i] == "--level" && i + 1 < a.size()) { level = std::atoi(a[++i].c_str()); have_level = true; }
+        else if (a[i].rfind("--level=", 0) == 0) { level = std::atoi(a[i].c_str() + 8); have_level = true; }
+        else if (a[i] == "--zstd" && i + 1 < a.size()) { ZstdParam p; if (!parse_zstd_param(a[++i], &p)) { std::fprintf(stderr, "error: invalid --zstd value\n"); return -1; } params.push_back(p); }
+        else if (a[i] == "--store") store = true;
+        else if (a[i] == "--split-blocks") split_blocks = true;                          // engine extension: ZARC_GPU_PX_BLOCK_SPLIT
+        else if (a[i] == "--check") check = true;                                        // engine extension: ZARC_GPU_PX_CHECK_FRAMES
+        else return 0;
+        return 1;
+    }
+    void apply(zarc::ArchiveWriter &enc) const
+    {
+        enc.set_zstd_parameter(ZARC_GPU_P_CHECKSUM_FLAG, 1); // pack.rs:227
+        if (have_level) enc.set_zstd_parameter(ZARC_GPU_P_COMPRESSION_LEVEL, level);
+        for (const auto &p : params) enc.set_zstd_parameter(p.id, p.value);
+        // What the engine does differently from libzstd with these is said once, on stderr and in the log: a level runs its tier's finder, the
+        // search-effort and long-distance-matching hints are accepted (the reference forwards them all, pack.rs:86-217) but change nothing.
+        if (have_level && level != 0 && zarc_gpu_level_finder(level) != level) {
+            std::fprintf(stderr, "warning: --level %d packs with the engine's level-%d finder (tiers: <= 1, 2..8, 9..14, 15..22)\n", level, zarc_gpu_level_finder(level));
+            LOGF(1, "level mapped to a finder tier", "level=%d finder=%d", level, zarc_gpu_level_finder(level));
+        }
+        for (const auto &p : params)
+            if (zarc_gpu_parameter_advisory(p.id)) {
+                std::fprintf(stderr, "warning: --zstd parameter %d=%d is accepted but advisory on this engine: the frames are the level's frames\n", p.id, p.value);
+                LOGF(1, "advisory zstd parameter", "id=%d value=%d", p.id, p.value);
+            }
+        if (store) enc.enable_compression(false);
+        if (split_blocks) enc.split_blocks(true);
+        if (check) enc.check_frames(true);
+    }
+};
 
 struct Walked { std::string path; struct stat st; bool is_link; std::string target; };
 void walk(const std::string &path, bool follow, std::vector<Walked> &out) // WalkDir::new(path).follow_links(follow), sorted
@@ -320,19 +367,14 @@ int cmd_pack(const std::vector<std::string> &a)
 {
     std::string output;
     std::vector<std::string> paths;
-    std::vector<ZstdParam> params;
-    bool store = false, follow = false, have_level = false, split_blocks = false, check = false;
-    int level = 0, gpus = 1;
+    EncoderFlags flags;
+    bool follow = false;
+    int gpus = 1;
     for (size_t i = 0; i < a.size(); i++) {
-        if (a[i] == "--output" && i + 1 < a.size()) output = a[++i];
-        else if (a[i] == "--level" && i + 1 < a.size()) { level = std::atoi(a[++i].c_str()); have_level = true; }
-        else if (a[i].rfind("--level=", 0) == 0) { level = std::atoi(a[i].c_str() + 8); have_level = true; }
-        else if (a[i] == "--zstd" && i + 1 < a.size()) { ZstdParam p; if (!parse_zstd_param(a[++i], &p)) { std::fprintf(stderr, "error: invalid --zstd value\n"); return 2; } params.push_back(p); }
-        else if (a[i] == "--store") store = true;
+        if (const int r = flags.parse(a, i)) { if (r < 0) return 2; }
+        else if (a[i] == "--output" && i + 1 < a.size()) output = a[++i];
         else if (a[i] == "-L" || a[i] == "--follow-symlinks") follow = true;
         else if (a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str()); // engine extension: deal every batch to N devices
-        else if (a[i] == "--split-blocks") split_blocks = true;                          // engine extension: ZARC_GPU_PX_BLOCK_SPLIT
-        else if (a[i] == "--check") check = true;                                        // engine extension: ZARC_GPU_PX_CHECK_FRAMES
         else if (!a[i].empty() && a[i][0] == '-') return usage();
         else paths.push_back(a[i]);
     }
@@ -343,27 +385,11 @@ int cmd_pack(const std::vector<std::string> &a)
     std::vector<int> devices;
     for (int d = 0; d < gpus; d++) devices.push_back(d);
     zarc::ArchiveWriter enc(file, devices);
-    enc.set_zstd_parameter(ZARC_GPU_P_CHECKSUM_FLAG, 1); // pack.rs:227
-    if (have_level) enc.set_zstd_parameter(ZARC_GPU_P_COMPRESSION_LEVEL, level);
-    for (const auto &p : params) enc.set_zstd_parameter(p.id, p.value);
-    // What the engine does differently from libzstd with these is said once, on stderr and in the log: a level runs its tier's finder, the
-    // search-effort and long-distance-matching hints are accepted (the reference forwards them all, pack.rs:86-217) but change nothing.
-    if (have_level && level != 0 && zarc_gpu_level_finder(level) != level) {
-        std::fprintf(stderr, "warning: --level %d packs with the engine's level-%d finder (tiers: <= 1, 2..8, 9..14, 15..22)\n", level, zarc_gpu_level_finder(level));
-        LOGF(1, "level mapped to a finder tier", "level=%d finder=%d", level, zarc_gpu_level_finder(level));
-    }
-    for (const auto &p : params)
-        if (zarc_gpu_parameter_advisory(p.id)) {
-            std::fprintf(stderr, "warning: --zstd parameter %d=%d is accepted but advisory on this engine: the frames are the level's frames\n", p.id, p.value);
-            LOGF(1, "advisory zstd parameter", "id=%d value=%d", p.id, p.value);
-        }
-    if (store) enc.enable_compression(false);
-    if (split_blocks) enc.split_blocks(true);
-    if (check) enc.check_frames(true);
+    flags.apply(enc);
 
     std::vector<Walked> entries;
     for (const auto &p : paths) walk(p, follow, entries);
-    LOGF(2, "walked", "entries=%zu devices=%d split_blocks=%d", entries.size(), gpus, split_blocks ? 1 : 0);
+    LOGF(2, "walked", "entries=%zu devices=%d split_blocks=%d", entries.size(), gpus, flags.split_blocks ? 1 : 0);
     // Contents go to the engine in batches of about 1 GiB.  A reader thread fills batch k+1 (file reads) while this thread has the
     // engine pack batch k and appends its frames to the archive; entries are added in walk order once their digest is known.
     struct Batch { size_t first = 0, last = 0; std::vector<std::vector<uint8_t>> contents; std::vector<size_t> owner; std::string error; };
@@ -696,6 +722,71 @@ int cmd_verify(const std::vector<std::string> &a)
     return failed ? 1 : 0;
 }
 
+// `zarc repack`: one archive into another.  The content frames are decoded, judged and encoded again on the device
+// (zarc_gpu_repack_batch through ArchiveWriter::repack_from): no file is created but the output, no content crosses PCIe raw, and the
+// directory -- owners, times, links, attributes, whatever this file system could not hold -- is carried over as it is.
+int cmd_repack(const std::vector<std::string> &a)
+{
+    std::string input, output, verify;
+    EncoderFlags flags;
+    bool keep_smaller = false;
+    int gpus = 1;
+    for (size_t i = 0; i < a.size(); i++) {
+        if (const int r = flags.parse(a, i)) { if (r < 0) return 2; }
+        else if (a[i] == "--output" && i + 1 < a.size()) output = a[++i];
+        else if (a[i] == "--verify" && i + 1 < a.size()) verify = a[++i];
+        else if (a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str());
+        else if (a[i] == "--keep-smaller") keep_smaller = true;
+        else if (!a[i].empty() && a[i][0] == '-') return usage();
+        else input = a[i];
+    }
+    if (input.empty() || output.empty() || gpus < 1 || gpus > 64) return usage();
+    if (gpus > zarc_gpu_device_count()) { std::fprintf(stderr, "Error: --gpus %d but %d device(s) are usable\n", gpus, zarc_gpu_device_count()); return 1; }
+    Mapped m(input);
+    std::vector<int> devices;
+    for (int d = 0; d < gpus; d++) devices.push_back(d);
+    zarc::ArchiveReader rd(m.p, m.n, devices);
+    const std::string in_digest = base64(rd.trailer().digest.bytes.data(), 32);
+    if (!verify.empty() && verify != in_digest) { std::fprintf(stderr, "Error: integrity failure: zarc file digest is %s\n", in_digest.c_str()); return 1; }
+    // written beside --output under a temporary name and renamed at the end: a run that fails leaves no file there
+    const std::string tmp = output + ".tmp." + std::to_string((long)getpid());
+    struct Temp { std::string path; bool keep = false; ~Temp() { if (!keep) (void)unlink(path.c_str()); } } temp{tmp};
+    zarc::RepackReport rep;
+    zarc::Digest digest;
+    {
+        std::ofstream file(tmp, std::ios::binary | std::ios::trunc);
+        if (!file) { std::fprintf(stderr, "Error: %s: %s\n", tmp.c_str(), std::strerror(errno)); temp.keep = true; return 1; }
+        zarc::ArchiveWriter enc(file, devices);
+        flags.apply(enc);
+        rep = enc.repack_from(rd, keep_smaller);
+        LOGF(2, "repacked", "frames=%zu kept=%zu devices=%d", rep.frames, rep.kept, gpus);
+        if (rep.bad.empty()) {
+            // the edition is carried over like the rest of the directory (editions are not repack's to make): the same input and flags
+            // give the same file, whenever and on however many devices
+            timespec now;
+            clock_gettime(CLOCK_REALTIME, &now);
+            digest = enc.finalise(rd.editions().empty() ? zarc::Timestamp{(int64_t)now.tv_sec, (uint32_t)now.tv_nsec} : rd.editions()[0].written_at);
+        }
+    }
+    if (!rep.bad.empty()) { // every bad frame with its digest and the files that use it; the output is given up
+        for (const auto &b : rep.bad) {
+            const std::string d64 = base64(b.digest.bytes.data(), 32);
+            const char *why = b.status == ZARC_GPU_FRAME_DIGEST ? "frame verification failed!" : zarc_gpu_frame_status_name(b.status);
+            size_t users = 0;
+            for (const zarc::File &f : rd.files())
+                if (f.digest && *f.digest == b.digest) { std::fprintf(stderr, "ERROR %s digest=%s path=%s\n", why, d64.c_str(), to_path(f.name).c_str()); users++; }
+            if (!users) std::fprintf(stderr, "ERROR %s digest=%s (no file uses this frame)\n", why, d64.c_str());
+        }
+        std::fprintf(stderr, "Error: %zu of %zu frames are not good: nothing was written to %s\n", rep.bad.size(), rep.frames, output.c_str());
+        return 1;
+    }
+    if (rename(tmp.c_str(), output.c_str()) != 0) { std::fprintf(stderr, "Error: %s: %s\n", output.c_str(), std::strerror(errno)); return 1; }
+    temp.keep = true;
+    std::printf("digest: %s\n", base64(digest.bytes.data(), 32).c_str());
+    std::fprintf(stderr, "repacked %zu frames (%llu -> %llu bytes), %zu kept\n", rep.frames, (unsigned long long)rep.old_bytes, (unsigned long long)rep.new_bytes, rep.kept);
+    return 0;
+}
+
 int cmd_list_files(const std::vector<std::string> &a)
 {
     std::string input;
@@ -736,7 +827,7 @@ int main(int argc, char **argv)
         else if (a == "--log-file") {
             have_log_file = true;
             // num_args = 0..=1: a following word that is not a subcommand is the path
-            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
+            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
         } else break;
     }
     if (i >= argc) return usage();
@@ -749,6 +840,7 @@ int main(int argc, char **argv)
         if (!verb.empty() && std::string("unpack").rfind(verb, 0) == 0) return cmd_unpack(rest);
         if (!verb.empty() && std::string("list-files").rfind(verb, 0) == 0) return cmd_list_files(rest);
         if (!verb.empty() && std::string("verify").rfind(verb, 0) == 0) return cmd_verify(rest);
+        if (!verb.empty() && std::string("repack").rfind(verb, 0) == 0) return cmd_repack(rest);
         return usage();
     } catch (const zarc::Error &e) {
         std::fprintf(stderr, "Error: %s\n", e.what());

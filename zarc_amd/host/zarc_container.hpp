@@ -280,6 +280,15 @@ struct Trailer { // trailer.rs
 };
 
 // ------------------------------------------------------------------ writer ------------------------------------
+class ArchiveReader;
+// What ArchiveWriter::repack_from found and did
+struct RepackReport {
+    size_t frames = 0, kept = 0;         // content frames of the input; of those, copied unchanged (keep_smaller)
+    uint64_t old_bytes = 0, new_bytes = 0; // their compressed bytes in the input / in the output
+    struct Bad { Digest digest; int status; };
+    std::vector<Bad> bad;                // frames that were not good (Encoder::Repacked::status), in archive order: the output is to be given up
+};
+
 class ArchiveWriter : public Encoder {
   public:
     explicit ArchiveWriter(std::ostream &w, int device = 0) : Encoder(w, device) {}
@@ -287,6 +296,12 @@ class ArchiveWriter : public Encoder {
 
     // Encoder::add_file_entry (add_file.rs:22-46)
     void add_file_entry(File f) { f.edition = 1; files_.push_back(std::move(f)); }
+
+    // One archive into another: every content frame of `src`, in archive-offset order and in batches of about 1 GiB of content, through
+    // Encoder::repack_frames (this writer's level / store mode / block splitting / read-back check), then every file entry carried over
+    // field for field.  Frame records are new (offset, length, edition 1); digests and uncompressed sizes are the input's.  finalise()
+    // is the caller's, as after add_file_entry.  Defined behind ArchiveReader.
+    RepackReport repack_from(const ArchiveReader &src, bool keep_smaller = false);
 
     // Encoder::finalise (encode/directory.rs:40-122): returns the directory digest
     Digest finalise(Timestamp written_at)
@@ -387,6 +402,8 @@ class ArchiveReader {
         parse_directory(res[0].data);
     }
     const Trailer &trailer() const { return trailer_; }
+    const uint8_t *data() const { return data_; } // the archive image
+    size_t size() const { return len_; }
     const std::vector<File> &files() const { return files_; }
     const std::map<Digest, Frame> &frames() const { return frames_; }
     const std::vector<Edition> &editions() const { return editions_; }
@@ -541,5 +558,32 @@ class ArchiveReader {
     std::vector<File> files_;
     std::map<Digest, Frame> frames_;
 };
+
+inline RepackReport ArchiveWriter::repack_from(const ArchiveReader &src, bool keep_smaller)
+{
+    RepackReport rep;
+    std::vector<Frame> all;
+    for (const auto &kv : src.frames()) all.push_back(kv.second);
+    std::stable_sort(all.begin(), all.end(), [](const Frame &a, const Frame &b) { return a.offset < b.offset; });
+    const uint64_t BATCH = (uint64_t)1 << 30;
+    size_t first = 0;
+    while (first < all.size()) {
+        size_t last = first;
+        uint64_t bytes = 0;
+        while (last < all.size() && (bytes < BATCH || last == first)) bytes += all[last++].uncompressed;
+        const std::vector<Frame> batch(all.begin() + (std::ptrdiff_t)first, all.begin() + (std::ptrdiff_t)last);
+        const std::vector<Repacked> res = repack_frames(src.data(), src.size(), batch, keep_smaller);
+        for (size_t k = 0; k < res.size(); k++) {
+            rep.frames++;
+            rep.old_bytes += res[k].old_length;
+            rep.new_bytes += res[k].new_length;
+            if (res[k].kept) rep.kept++;
+            if (res[k].status != ZARC_GPU_FRAME_OK) rep.bad.push_back(RepackReport::Bad{batch[k].digest, res[k].status});
+        }
+        first = last;
+    }
+    for (const File &f : src.files()) add_file_entry(f);
+    return rep;
+}
 
 } // namespace zarc

@@ -8,6 +8,8 @@
 //   zarc::Frame              crates/zarc/src/directory/frame.rs:10-32
 //   zarc::Digest             crates/zarc/src/integrity.rs:14-36 (constant-time equality :17-22)
 //   zarc::FrameReader        crates/zarc/src/decode/frame_iterator.rs:14-104 (read_content_frame + verify)
+//   Encoder::repack_frames   read_content_frame joined to add_data_frame on the device (zarc_gpu_repack_batch): the frames of another
+//                            archive become frames of this one without their content passing through host memory
 //
 // What differs, on purpose: the engine is batched, so `add_data_frames` takes many entries at once (frames
 // are independent: a fresh session per frame, content_frame.rs:37-39).  Call order is preserved: frame order
@@ -122,6 +124,18 @@ inline void cap_copy_threads(const std::vector<std::unique_ptr<Engine>> &engines
     if (g <= 2) return;
     const int per = (int)std::max<size_t>(2, 16 / g);
     for (auto &e : engines) e->check(zarc_gpu_set_parameter(e->get(), ZARC_GPU_PX_COPY_THREADS, per));
+}
+
+// Directory records come out of an archive and are untrusted: no u64 wrap-around, no frame beyond the file, no allocation the engine
+// would refuse anyway (FrameReader and Encoder::repack_frames look at them before anything is sized by them)
+inline void check_frame_records(size_t archive_len, const std::vector<Frame> &wanted)
+{
+    for (const Frame &f : wanted) {
+        if (f.length > archive_len || f.offset > archive_len - f.length) throw Error(ZARC_GPU_E_PARAM, "frame outside the archive");
+        if (f.uncompressed >= 0xFFFFFFF0ull || f.length >= 0xFFFFFFF0ull) throw Error(ZARC_GPU_E_UNSUPPORTED, "frames of 4 GiB or more are not supported");
+        // Zstandard cannot expand a frame by more than a factor of ~(128 KiB block from a 4-byte RLE block): a larger claim is corrupt
+        if (f.uncompressed > (f.length + 16) * (uint64_t)65536) throw Error(ZARC_GPU_E_PARAM, "frame claims an impossible uncompressed size");
+    }
 }
 
 class Encoder {
@@ -241,6 +255,87 @@ class Encoder {
         }
         return digests;
     }
+    // What became of one frame handed to repack_frames
+    struct Repacked {
+        int status = ZARC_GPU_FRAME_OK; // FrameIterator::verify()'s answer for the OLD frame (zarc_gpu_verify_batch's status); ZARC_GPU_FRAME_CORRUPT
+                                        // with check_frames(true): the NEW frame failed its read-back check.  Only OK frames are written
+        Digest digest;                  // BLAKE3 of what the old frame decoded to
+        uint64_t old_length = 0, new_length = 0; // new_length: what was written (the old length for a kept frame, 0 for a refused one)
+        bool kept = false;              // keep_smaller: the new frame was not smaller, the old bytes were copied
+    };
+    // Decoder::read_content_frame joined to add_data_frame for a batch: `wanted` are directory records of the archive image `archive`
+    // (offset / length / uncompressed / digest).  Every frame is judged as FrameReader::check_content_frames judges it, and the good ones
+    // are encoded again with THIS encoder's parameters -- on the device, out of the scratch they were decoded into -- and appended in the
+    // order of `wanted` with new records (offset, length, this edition; digest and uncompressed size unchanged).  The batch is dealt to
+    // the devices by uncompressed bytes with shard_assign and the results are appended in the caller's order: G devices write the bytes
+    // one would.  A digest this encoder has a frame for already is skipped, as in add_data_frames.  Frames that are not good are
+    // reported and not written; it is the caller's to give up the archive.  keep_smaller: a new frame that is not smaller than the old
+    // one is dropped and the old bytes are copied.
+    std::vector<Repacked> repack_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, bool keep_smaller = false)
+    {
+        const size_t n = wanted.size();
+        std::vector<Repacked> out(n);
+        check_frame_records(archive_len, wanted);
+        if (n == 0) return out;
+        std::vector<size_t> rl(n);
+        for (size_t i = 0; i < n; i++) rl[i] = (size_t)wanted[i].uncompressed;
+        const size_t g = engines_.size();
+        const auto share = shard_assign(rl.data(), n, g);
+        std::vector<std::vector<uint8_t>> buffers(g);
+        std::vector<const uint8_t *> made(n, nullptr);
+        std::vector<int> rc(g, ZARC_GPU_OK);
+        auto repack_share = [&](size_t d) {
+            const std::vector<size_t> &idx = share[d];
+            const size_t m = idx.size();
+            if (m == 0) return;
+            std::vector<const void *> fp(m);
+            std::vector<size_t> fl(m), ul(m), off(m), out_len(m);
+            std::vector<Digest> expect(m), got(m);
+            std::vector<int> status(m);
+            size_t cap = 0;
+            for (size_t j = 0; j < m; j++) {
+                const Frame &f = wanted[idx[j]];
+                fp[j] = archive + f.offset; fl[j] = (size_t)f.length; ul[j] = (size_t)f.uncompressed; expect[j] = f.digest; cap += zarc_gpu_bound(ul[j]);
+            }
+            buffers[d].resize(cap);
+            rc[d] = zarc_gpu_repack_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), buffers[d].data(), cap,
+                                          off.data(), out_len.data(), (uint8_t(*)[32])got.data(), status.data());
+            if (rc[d] != ZARC_GPU_OK && rc[d] != ZARC_GPU_E_CHECK) return;
+            for (size_t j = 0; j < m; j++) { // (every share writes its own entries of out / made)
+                Repacked &r = out[idx[j]];
+                r.status = status[j]; r.digest = got[j]; r.old_length = fl[j]; r.new_length = out_len[j];
+                made[idx[j]] = buffers[d].data() + off[j];
+            }
+        };
+        if (g == 1) repack_share(0);
+        else {
+            std::vector<std::thread> th;
+            for (size_t d = 0; d < g; d++) th.emplace_back(repack_share, d);
+            for (auto &t : th) t.join();
+        }
+        bool check_failed = false;
+        for (size_t d = 0; d < g; d++) { if (rc[d] == ZARC_GPU_E_CHECK) check_failed = true; else engines_[d]->check(rc[d]); }
+        for (size_t k = 0; k < n; k++) {
+            Repacked &r = out[k];
+            if (r.status != ZARC_GPU_FRAME_OK || check_failed) { r.new_length = 0; continue; } // (a failed read-back check voids the whole call)
+            if (frames_.count(wanted[k].digest)) { r.new_length = frames_.at(wanted[k].digest).length; continue; } // "frame already exists, skipping"
+            const uint8_t *at = made[k];
+            if (keep_smaller && r.new_length >= r.old_length) { r.kept = true; r.new_length = r.old_length; at = archive + wanted[k].offset; }
+            Frame f;
+            f.edition = edition_;
+            f.offset = offset_;
+            f.digest = wanted[k].digest;
+            f.length = r.new_length;
+            f.uncompressed = wanted[k].uncompressed;
+            writer_.write((const char *)at, (std::streamsize)f.length);
+            if (!writer_) throw Error(ZARC_GPU_E_DEVICE, "write failed");
+            offset_ += f.length;
+            frames_.emplace(f.digest, f);
+            order_.push_back(f.digest);
+        }
+        return out;
+    }
+
     // hash-first dedup (default on; off = every entry is compressed and duplicates are dropped afterwards: same archive, more work)
     void set_hash_first(bool on) { hash_first_ = on; }
 
@@ -304,12 +399,8 @@ class FrameReader {
         const size_t n = wanted.size();
         std::vector<Result> out(n);
         std::vector<size_t> rl(n);
+        check_frame_records(archive_len, wanted);
         for (size_t i = 0; i < n; i++) {
-            // untrusted directory records: no u64 wrap-around, no frame beyond the file, no allocation the engine would refuse anyway
-            if (wanted[i].length > archive_len || wanted[i].offset > archive_len - wanted[i].length) throw Error(ZARC_GPU_E_PARAM, "frame outside the archive");
-            if (wanted[i].uncompressed >= 0xFFFFFFF0ull || wanted[i].length >= 0xFFFFFFF0ull) throw Error(ZARC_GPU_E_UNSUPPORTED, "frames of 4 GiB or more are not supported");
-            // Zstandard cannot expand a frame by more than a factor of ~(128 KiB block from a 4-byte RLE block): a larger claim is corrupt
-            if (wanted[i].uncompressed > (wanted[i].length + 16) * (uint64_t)65536) throw Error(ZARC_GPU_E_PARAM, "frame claims an impossible uncompressed size");
             if (with_data) out[i].data.resize(wanted[i].uncompressed);
             rl[i] = wanted[i].uncompressed;
         }
