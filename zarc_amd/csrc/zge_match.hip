@@ -8,8 +8,8 @@
 // 4-byte "short" hash table of 2^13 u32 entries each, an entry packing (position+1) << 10 | 10 hash check bits -- are 64 KiB of LDS
 // and stay there for the whole frame, so matches reach back across all earlier blocks (64 KiB / the 2 MiB table segment).  The kernel is bound by VALU issue and by barrier / L2 waits, not by HBM.
 // A block (<= 64 KiB: ZARC_BLOCK) is swept in tiles of 1024 positions, two positions per thread (t and t+512):
-//   S0/S1 the tile's window (recent-offset range before it, compare overrun after it) goes to LDS -- the dword of the
-//         NEXT tile is requested now and parked in a register; every position is hashed (32-bit multiplies)
+//   S0/S1 the tile's window (recent-offset range before it, compare overrun after it) is in LDS since the previous tile; the NEXT
+//         tile's, parked in a register since the previous tile, goes to the other buffer; every position is hashed (32-bit multiplies)
 //   S2    ordered lookup + insert, one wave per table, 64 positions per step: LDS executes one wave's instructions
 //         in order, so a position sees every insert of earlier 64-groups with no waiting between steps
 //   S3    every position scores its candidates: one 16-byte request source[-8..8) per table candidate (first compare
@@ -17,8 +17,8 @@
 //         comparisons advance 16 bytes per LDS / global round trip; offers for backward propagation are posted with ds_max
 //   far   a third (level >= 9: up to eight more) candidate per position comes from far tables in HBM (one slab per workgroup):
 //         same entry format, but only every 2^far_step_log-th position is inserted (entries live that much longer) and a tile's
-//         lookups see the inserts of EARLIER tiles only -- lookups are issued in S1 and land during S2, inserts are fire-and-forget
-//         atomic max after S3, so neither is on the tile's critical path and no order inside a tile is needed
+//         lookups see the inserts of EARLIER tiles only -- the entries of tile T+1 are requested at the top of S3 of tile T, inserts are
+//         fire-and-forget atomic max behind the S4 barrier, so neither is on the tile's critical path and no order inside a tile is needed
 //   S4    backward propagation: position t may start the match found at t+k, k bytes earlier
 //   S5    one-byte lazy rule -> take flag and successor next[t] for every position
 //   S6    the greedy parse IS the path from the entry cursor through next[]: per 64-position chunk the exit of
@@ -27,6 +27,18 @@
 //   S7    ballot/popcount prefix sums (16-lane scan over the chunks) place literal bytes and sequences
 //   A tile in which no position found a match takes an all-literals path after S3; after two such tiles in a row the next
 //   1, 3, then 7 tiles are not searched at all (cold stretch: bytes go straight to the literals, nothing is inserted).
+// Memory requests of a tile T and where each is waited for (vector-memory results return in order and the counter is drained as a
+// whole, so what matters is which requests are in flight at each wait; tools/spills.sh counts the waits of the tile loop):
+//   window of T+2   one global_load_dword per thread (an offset from the frame base: never a flat load) behind the S4 barrier, ahead of
+//                   the far inserts; nothing waits on the VM counter until S0 of T+1 stores it to LDS (that wait also takes the
+//                   acknowledgements of T's S7 stores and far inserts, issued 4 stages earlier / just before the top barrier)
+//   far sources     of T (8 bytes per far candidate) in S1, entries at hand; waited for in front of the S2 -> S3 barrier, where seven
+//                   of eight waves wait for the table wave anyway -- the same wait completes the far inserts of T-1
+//   far entries     of T+1 at the top of S3, then the near sources (16 bytes per head position); the first compare waits for both (the
+//                   recent-offset guesses, LDS only, run in between), later 16-byte steps are dependent round trips
+//   all of these    are complete in front of the S4 barrier (the visibility rule: no insert of T is sent before every wave holds
+//                   its entries of T+1); behind it: window request, far inserts, S7's stores -- none waited for inside T
+// A tile that is not searched (cursor past it, cold stretch) and the first tile behind one request what they lack on the spot.
 // Output per block: packed (literal position, match length, offset) + literal bytes in HBM scratch; literal
 // lengths and repcodes are resolved by the entropy stage.  Deterministic and bit-identical to
 // oracle/zstd_enc_model.c (tests/ compare them).
@@ -146,8 +158,12 @@ __device__ __forceinline__ uint32_t wave_match_ext(const uint8_t *src, uint32_t 
 }
 
 // The window of a tile staged in LDS: frame bytes [lo, hi) = rep_back + 8 bytes before the tile .. cap + 16 after it,
-// fetched as whole dwords starting at the aligned address `w` (one dword per thread: TB_BYTES / 4 <= THREADS).
-struct StageWin { const uint32_t *w; int ndw; uint32_t wofs; };
+// fetched as whole dwords starting at the aligned byte offset `at` from the frame base (one dword per thread: TB_BYTES / 4 <= THREADS).
+// `at` is an offset from `src` (negative by up to 3 where the base itself is misaligned), never a pointer rebuilt from an integer: the
+// loads then keep the address space of `src` and compile to global_load_dword.  A pointer made from a uintptr_t compiles to
+// flat_load_dword, which counts on the LDS counter as well and is waited for with vmcnt(0) lgkmcnt(0) at the next LDS read -- a
+// prefetch is then drained a few instructions after it was issued.
+struct StageWin { int64_t at; int ndw; uint32_t wofs; }; // at: 64-bit -- positions are unsigned 32-bit (entries of up to 4 GiB), and it may be -3
 static_assert((TB_BYTES + 3) / 4 <= THREADS, "one staged dword per thread");
 __device__ __forceinline__ StageWin stage_window(const ZgeParams &P, const uint8_t *src, uint32_t n, uint32_t tile, uint32_t tend, uint32_t cap_max)
 {
@@ -156,13 +172,18 @@ __device__ __forceinline__ StageWin stage_window(const ZgeParams &P, const uint8
     const uint32_t lo = tile >= before ? tile - before : 0;
     uint32_t hi = tend + cap_max + 16;
     if (hi > n + 16) hi = n + 16; // the arena is padded by ZARC_GPU_PAD
-    const uintptr_t a = (uintptr_t)(src + lo);
-    const uint32_t mis = (uint32_t)(a & 3);
+    const uint32_t mis = (uint32_t)(((uintptr_t)src + lo) & 3);
     StageWin s;
-    s.w = (const uint32_t *)(a - mis);
+    s.at = (int64_t)lo - (int64_t)mis;
     s.ndw = (int)((hi - lo + mis + 3) / 4);
     s.wofs = mis - lo;
     return s;
+}
+// dword `i` of a staged window
+__device__ __forceinline__ uint32_t window_dword(const uint8_t *src, const StageWin &s, int i)
+{
+    const uint8_t *const first = src + s.at; // uniform: scalar registers; the lane's part stays a 32-bit offset
+    return *(const uint32_t *)__builtin_assume_aligned(first + 4u * (uint32_t)i, 4);
 }
 
 // end of the tile that starts at `tile`: tiles never straddle a block
@@ -270,7 +291,9 @@ __device__ __forceinline__ void zge_match_body(MatchLds<TAB_LOG, NEAR16> &L, con
     uint32_t pf_far_tile = 0xFFFFFFFFu; // the tile fnext[] belongs to
     uint32_t hfn[PER] = {0xFFFFFFFFu, 0xFFFFFFFFu}; // FAR_CDC: bucket | check bits of this thread's positions of that tile (0xFFFFFFFF: not a far position)
     // Tile windows are staged two tiles ahead: at the top of tile T the window of T+1 goes to the other LDS buffer (it was requested
-    // during T-1 and sits in a register) and the window of T+2 is requested.  S1 hashes the next tile's positions out of that buffer.
+    // during T-1 and sits in a register); the window of T+2 is requested behind T's S4 barrier.  S3 hashes the next tile's far positions
+    // out of that buffer.  pf_tile says which tile pf_word belongs to: a tile that leaves early (cursor already past it, cold stretch)
+    // or is never entered (RLE block) requests nothing, and the next searched tile then loads what it lacks on the spot.
     uint32_t pf_word = 0, pf_tile = 0xFFFFFFFFu;            // this thread's dword of the window of tile `pf_tile`
     uint32_t lds_tile[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};     // the tile whose window each LDS buffer holds (uniform)
 #pragma unroll
@@ -383,7 +406,7 @@ __device__ __forceinline__ void zge_match_body(MatchLds<TAB_LOG, NEAR16> &L, con
                 // this tile's window: normally staged while the previous tile was worked on
                 if (lds_tile[bsel] != tile) {
                     uint32_t v = pf_word;
-                    if (pf_tile != tile && tid < sw.ndw) v = sw.w[tid]; // first tile of a frame, or after skipped tiles
+                    if (pf_tile != tile && tid < sw.ndw) v = window_dword(src, sw, tid); // first tile of a frame, or after skipped tiles
                     if (tid < sw.ndw) L.tb[bsel][tid] = v;
                     lds_tile[bsel] = tile;
                     staged_now = true;
@@ -392,16 +415,12 @@ __device__ __forceinline__ void zge_match_body(MatchLds<TAB_LOG, NEAR16> &L, con
                     const StageWin nw = stage_window(P, src, n, ntile, tile_end(ntile, n), cap_max);
                     wofs_n = nw.wofs;
                     uint32_t v = pf_word;
-                    if (pf_tile != ntile && tid < nw.ndw) v = nw.w[tid];
+                    if (pf_tile != ntile && tid < nw.ndw) v = window_dword(src, nw, tid);
                     if (tid < nw.ndw) L.tb[bsel ^ 1u][tid] = v;
                     lds_tile[bsel ^ 1u] = ntile;
-                    // request the window of the tile after that now: it arrives while this tile is being worked on
-                    const uint32_t n2 = ntile + TILE;
-                    if (n2 < n) {
-                        const StageWin w2 = stage_window(P, src, n, n2, tile_end(n2, n), cap_max);
-                        if (tid < w2.ndw) pf_word = w2.w[tid];
-                        pf_tile = n2;
-                    }
+                    // (the window of the tile after that is requested behind the S4 barrier, zge_parse_round.h: from there to this
+                    // point of the next tile the wave issues stores, atomics and LDS work only, so nothing waits on the VM counter
+                    // while the request is in flight.  Requested here, it was drained by S1's first wait, 25 instructions on.)
                 }
             }
             // In the steady state this tile's window has been in LDS since the previous tile and the one written above (the next

@@ -36,6 +36,16 @@
             zd::lds_barrier(); // own matches (a0) and offers (ex) are complete
 #if ZGE_FIRST
             ZGE_PROF(4);
+            { // The window of the tile after the next, parked in a register until that tile's predecessor stages it (S0).  Issued here,
+              // ahead of the far inserts: the rest of the tile is stores, atomics and LDS work, no wait on the VM counter before the next
+              // tile's S0 -- and the all-literals exit below leaves with the request made.
+                const uint32_t n2 = ntile + TILE;
+                if (n2 < n) {
+                    const StageWin w2 = stage_window(P, src, n, n2, tile_end(n2, n), cap_max);
+                    if (tid < w2.ndw) pf_word = window_dword(src, w2, tid);
+                    pf_tile = n2;
+                }
+            }
             if (NFAR) {
                 // far inserts of this tile: every wave has used its lookups (they fed S3), so none of them can see these.  Every
                 // 2^far_step_log-th position, into the way of this tile; atomic max = the highest position wins, whatever the order.
