@@ -43,7 +43,8 @@ extern "C" {
                                   zarc_gpu_verify_batch*, zarc_gpu_last_copy_bytes, ZARC_GPU_PX_CHECK_FRAMES and ZARC_GPU_E_CHECK were added WITHOUT a new
                                   version (they are new symbols and new ids; nothing older changed): a library from before them fails a caller
                                   that wants them at the symbol lookup, not by version.  zarc_gpu_repack_batch* joined them the same way, for the
-                                  same reason */
+                                  same reason, and zarc_gpu_search_batch* with ZARC_GPU_T_SEARCH after them (ZARC_GPU_T_COUNT grew from 10 to 11:
+                                  zarc_gpu_last_kernel_ms of an older library answers < 0 for the new id, as for any id it does not know) */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -282,6 +283,35 @@ int zarc_gpu_repack_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_b
                                  const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, void *d_dst, size_t dst_cap,
                                  uint64_t *dst_off, uint64_t *dst_len, uint8_t *digest /* n*32 */, int *status);
 
+/* ---- search: which frames contain a byte string, without the content leaving the device ------------------------ */
+/* What `zstdgrep -c -F` answers per file, for a batch of frames (the reference has no such call: it would unpack everything and scan on
+ * the host).  Every frame is decoded and judged as zarc_gpu_verify_batch does it, and a kernel then looks through the decoded bytes where
+ * they lie for ONE fixed byte string -- no regular expression -- of 1 .. ZARC_GPU_SEARCH_MAX_PATTERN bytes.
+ *   - status[i] and digest[i] are EXACTLY what zarc_gpu_verify_batch gives for the same frame and `expect`.
+ *   - count[i] = the number of start positions p with content[p .. p + pattern_len) == pattern (overlapping occurrences count; a match
+ *     never crosses a frame's end); first[i] = the lowest such p, or ZARC_GPU_SEARCH_NONE.
+ *   - A frame is searched when it decoded: status ZARC_GPU_FRAME_OK, and ZARC_GPU_FRAME_DIGEST as well (content that differs from
+ *     `expect` is still delivered by unpack).  Every other status: count 0, first ZARC_GPU_SEARCH_NONE.
+ *   - ZARC_GPU_SEARCH_ICASE folds the ASCII letters 'A'..'Z' / 'a'..'z' in pattern and content and NOTHING else: '@' '[' '`' '{' and every
+ *     byte >= 0x80 match only themselves.
+ *   - pattern == NULL, pattern_len == 0 or above the maximum, unknown flag bits, a missing digest / status / count / first array:
+ *     ZARC_GPU_E_PARAM.  n == 0: ZARC_GPU_OK.  A frame or raw length of 4 GiB or more: ZARC_GPU_E_UNSUPPORTED.
+ *   - The decoded bytes count against ZARC_GPU_PX_SCRATCH_MB exactly as verify's do; the results are the same for every budget.
+ *   - The host form moves the frames host-to-device (sum of frame_len) and no content back: zarc_gpu_last_copy_bytes reports exactly that
+ *     (the pattern is not content).  The device form reports 0.
+ *   - Cost: one pass over the decoded bytes beside the two hash passes.  The worst case is a pattern whose first four bytes match almost
+ *     everywhere (a run of one byte searched for that byte repeated): then every position is compared in full, O(content * pattern_len).
+ *   - zarc_gpu_last_kernel_ms: verify's timers, ZARC_GPU_T_SEARCH for the search kernel, ZARC_GPU_T_TOTAL including it. */
+#define ZARC_GPU_SEARCH_MAX_PATTERN 256
+#define ZARC_GPU_SEARCH_NONE UINT64_MAX           /* first[i] of a frame without a match */
+enum { ZARC_GPU_SEARCH_ICASE = 1 };               /* flags; any other bit: ZARC_GPU_E_PARAM */
+int zarc_gpu_search_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                          const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const void *pattern, size_t pattern_len, unsigned flags,
+                          uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first);
+int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                 const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const void *pattern /* HOST pointer */,
+                                 size_t pattern_len, unsigned flags, uint8_t *digest /* n*32 */, int *status, uint64_t *count, uint64_t *first);
+
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN]);
@@ -306,7 +336,8 @@ enum {
     ZARC_GPU_T_DEC_SEQS = 7,  /* decoder stage 2: sequence entropy decoding (zarc_zdec_seqs)             */
     ZARC_GPU_T_DEC_LITS = 8,  /* decoder stage 2: Huffman literals (zarc_zdec_literals, side stream)      */
     ZARC_GPU_T_DEC_FRAMES = 9,/* decoder frame pass (zarc_zstd_frames + the inline decoder for the rest)  */
-    ZARC_GPU_T_COUNT = 10
+    ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan, summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_COUNT = 11
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);
 /* Content bytes the most recent batch call moved between host and device (descriptor arrays, statuses, digests not counted).  Every

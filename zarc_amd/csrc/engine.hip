@@ -112,6 +112,8 @@ struct zarc_gpu {
     // repack (zarc_gpu_repack_batch*): the decode half leaves its bytes in d_vout and the encode half reads them there
     DevBuf d_vout2;             // read-back check inside a repack pass: d_vout holds the sources, the check decodes into this one
     DevBuf d_rp_order, d_rp_xxh; // zarc_repack_plan: the caller's index of every frame of the decoder's order; XXH64 by entry for frame assembly
+    // search (zarc_gpu_search_batch*): zarc_search_scan over d_vout behind the verdict of a verify pass
+    DevBuf d_srch_pat, d_srch_slices, d_srch_count, d_srch_first; // the (folded) pattern; slice prefix, matches and lowest match of every frame (decoder order)
     bool vout_busy = false;     // a repack pass is between its halves: d_vout is not the check's to take
     uint64_t dec_scratch = 0;   // decoder scratch (sequences, literals, tables) of the most recent decode, as counted against the budget
     // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
@@ -619,8 +621,17 @@ struct PackPlanned {
     size_t budget;             // encoder scratch budget of this pass (0 = the handle's)
 };
 
+// A verify pass that also searches what it decoded (zarc_gpu_search_batch*): zarc_search_scan runs behind the verdict, per part, while that
+// part's bytes are in d_vout
+struct SearchReq {
+    const uint8_t *d_pattern;  // device: the pattern, folded when icase
+    uint32_t m, icase;
+    uint64_t *count, *first;   // host, in the caller's order: matching start positions; the lowest, or ZARC_GPU_SEARCH_NONE
+};
+
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, void *d_dst_base,
-                        const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk);
+                        const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk,
+                        const SearchReq *srch = nullptr);
 int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, uint64_t *dst_len,
                int *status, bool trailer, const PackPlanned *pl = nullptr);
 void check_message(zarc_gpu_t *h, size_t index);
@@ -1054,7 +1065,7 @@ constexpr int UNPACK_SPLIT = -1000; // internal: the decoder's scratch for this 
 // own_out: bytes of engine-owned output scratch this call decodes into (verify, read-back check); they count against the budget
 int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off_in, const uint64_t *frame_len_in,
                        void *d_dst_base, const uint64_t *dst_off_in, const uint64_t *raw_len_in, const uint8_t *expect_in, uint8_t *digest,
-                       int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr, DevBuf *order_out = nullptr)
+                       int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr, DevBuf *order_out = nullptr, const SearchReq *srch = nullptr)
 {
     int rc = 0;
     h->dec_scratch = 0;
@@ -1486,6 +1497,23 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
                        h->d_stored_ck.as<uint32_t>(), h->d_digests.as<uint32_t>(), expect_in ? h->d_expect.as<uint32_t>() : (const uint32_t *)nullptr,
                        h->d_status.as<int32_t>());
     ZHIP(hipGetLastError());
+    int e5 = -1, e6 = -1;
+    if (srch) { // ---- search: the decoded bytes are judged; look through those of the frames that decoded, where they lie
+        std::vector<uint64_t> slices(n + 1, 0);
+        for (size_t i = 0; i < n; i++) slices[i + 1] = slices[i] + std::max<uint64_t>(1, (raw_len[i] + ZARC_CHECK_SLICE - 1) / ZARC_CHECK_SLICE);
+        if (slices[n] > 0x7FFFFFFFull) { set_error(h, "search: batch too large"); return ZARC_GPU_E_PARAM; }
+        if ((rc = upload_u64(h, h->d_srch_slices, slices.data(), n + 1))) return rc;
+        ZHIP(h->d_srch_count.reserve(n * 4));
+        ZHIP(h->d_srch_first.reserve(n * 4));
+        ZHIP(hipMemsetAsync(h->d_srch_count.p, 0, n * 4, h->stream));
+        ZHIP(hipMemsetAsync(h->d_srch_first.p, 0xFF, n * 4, h->stream));
+        ZHIP(t.mark(&e5));
+        hipLaunchKernelGGL(zarc_search_scan, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                           b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_pattern, srch->m, srch->icase,
+                           h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>());
+        ZHIP(hipGetLastError());
+        ZHIP(t.mark(&e6));
+    }
     std::vector<int32_t> st_v;
     std::vector<uint8_t> dg_v;
     int32_t *st = (int32_t *)meta_take(h, n * 4); // results come back through the page-locked arena too, then go to the caller's order
@@ -1494,8 +1522,15 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (!dg) { dg_v.resize(n * 32); dg = dg_v.data(); }
     ZHIP(hipMemcpyAsync(st, h->d_status.p, n * 4, hipMemcpyDeviceToHost, h->stream));
     ZHIP(hipMemcpyAsync(dg, h->d_digests.p, n * 32, hipMemcpyDeviceToHost, h->stream));
+    std::vector<uint32_t> sc, sf;
+    if (srch) {
+        sc.resize(n); sf.resize(n);
+        ZHIP(hipMemcpyAsync(sc.data(), h->d_srch_count.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+        ZHIP(hipMemcpyAsync(sf.data(), h->d_srch_first.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+    }
     ZHIP(hipStreamSynchronize(h->stream));
     for (size_t i = 0; i < n; i++) { status[order[i]] = st[i]; memcpy(digest + (size_t)order[i] * 32, dg + i * 32, 32); }
+    if (srch) for (size_t i = 0; i < n; i++) { srch->count[order[i]] = sc[i]; srch->first[order[i]] = sf[i] == 0xFFFFFFFFu ? ZARC_GPU_SEARCH_NONE : sf[i]; }
     if (fastpath && diag_env("ZARC_GPU_DEC_STATS", 0)) { // diagnostics: how many frames had their sequences decoded ahead
         std::vector<uint32_t> fl(n);
         ZHIP(hipMemcpy(fl.data(), h->d_fast.p, n * 4, hipMemcpyDeviceToHost));
@@ -1528,6 +1563,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     h->ms[ZARC_GPU_T_XXH64] = t_xxh; // side stream: overlaps the digest pass
     h->ms[ZARC_GPU_T_BLAKE3] = t_b3;
     h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e3);
+    if (srch) { h->ms[ZARC_GPU_T_SEARCH] = elapsed(h, e5, e6); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e6); }
     return ZARC_GPU_OK;
 }
 
@@ -1539,7 +1575,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
 // that does not fit the device is halved after; a single frame runs alone whatever its size.
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                         void *d_dst_base, const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status,
-                        const PackCheck *chk = nullptr)
+                        const PackCheck *chk = nullptr, const SearchReq *srch)
 {
     const bool own = d_dst_base == nullptr;
     DevBuf &vout = h->vout_busy ? h->d_vout2 : h->d_vout; // (the read-back check inside a repack pass: d_vout holds what it compares with)
@@ -1558,7 +1594,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
     }
     if (attempt)
         rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, own ? vout.p : d_dst_base, own ? nullptr : dst_off, raw_len, expect, digest,
-                                status, own_bytes, chk);
+                                status, own_bytes, chk, nullptr, srch);
     if ((rc != UNPACK_SPLIT && rc != ZARC_GPU_E_NOMEM) || n < 2) return rc == UNPACK_SPLIT ? ZARC_GPU_E_NOMEM : rc;
     (void)hipStreamSynchronize(h->stream);
     if (rc == ZARC_GPU_E_NOMEM) {
@@ -1577,8 +1613,10 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
         const size_t a = part[p], m = part[p + 1] - a;
         PackCheck sub{};
         if (chk) { sub = *chk; sub.first_bad += a; if (chk->entry_map) sub.entry_map += a; else sub.entry0 += (uint32_t)a; }
+        SearchReq ssub{};
+        if (srch) { ssub = *srch; ssub.count += a; ssub.first += a; }
         rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
-                                 digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr);
+                                 digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr);
         if (rc) return rc;
         for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] += h->ms[i];
     }
@@ -1608,6 +1646,48 @@ int zarc_gpu_verify_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_b
     if (n == 0) return ZARC_GPU_OK;
     if (!d_frames_base || !frame_off || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
     return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status);
+}
+
+} // extern "C"
+namespace {
+// the arguments every search entry point checks the same way, before anything else is looked at
+int search_check_args(zarc_gpu_t *h, const void *pattern, size_t pattern_len, unsigned flags, const void *digest, const int *status, const uint64_t *count,
+                      const uint64_t *first)
+{
+    if (!h) return ZARC_GPU_E_PARAM;
+    if (!pattern || pattern_len == 0 || pattern_len > ZARC_GPU_SEARCH_MAX_PATTERN) { set_error(h, "search: the pattern has 1 to 256 bytes"); return ZARC_GPU_E_PARAM; }
+    if (flags & ~(unsigned)ZARC_GPU_SEARCH_ICASE) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
+    if (!digest || !status || !count || !first) return ZARC_GPU_E_PARAM;
+    return 0;
+}
+// the pattern goes up once per call, folded here when the text is folded there ('A'..'Z' only)
+int search_upload_pattern(zarc_gpu_t *h, const void *pattern, size_t pattern_len, unsigned flags)
+{
+    uint8_t pat[ZARC_GPU_SEARCH_MAX_PATTERN] = {0};
+    memcpy(pat, pattern, pattern_len);
+    if (flags & ZARC_GPU_SEARCH_ICASE) for (size_t k = 0; k < pattern_len; k++) if (pat[k] >= 'A' && pat[k] <= 'Z') pat[k] |= 0x20;
+    ZHIP(h->d_srch_pat.reserve(sizeof pat));
+    ZHIP(hipMemcpy(h->d_srch_pat.p, pat, sizeof pat, hipMemcpyHostToDevice));
+    return 0;
+}
+} // namespace
+extern "C" {
+
+// zarc_gpu_verify_batch_device with zarc_search_scan behind the verdict of every part
+int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                 const uint64_t *raw_len, const uint8_t *expect, const void *pattern, size_t pattern_len, unsigned flags,
+                                 uint8_t *digest, int *status, uint64_t *count, uint64_t *first)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if ((rc = search_check_args(h, pattern, pattern_len, flags, digest, status, count, first))) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
+    for (size_t i = 0; i < n; i++)
+        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
+    if (!h->nested && (rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc; // (the host form has done it for all its chunks)
+    const SearchReq srch{h->d_srch_pat.as<uint8_t>(), (uint32_t)pattern_len, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
+    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
 }
 
 
@@ -2133,12 +2213,14 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 // The chunk loop of zarc_gpu_unpack_batch without its outbound half: chunk c+1's frames come in while chunk c is decoded and judged;
 // nothing but statuses and digests goes back.  A chunk's decoded bytes live in the handle's scratch (unpack_device_split), so the
 // chunks are cut by the same weight as unpack's.
-int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
-                          const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status)
+// With a pattern (zarc_gpu_search_batch) every chunk is searched as well, and two more words per frame go back.
+} // extern "C"
+namespace {
+int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                     const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const void *pattern,
+                     size_t pattern_len, unsigned flags, uint64_t *count, uint64_t *first)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if (n == 0) return ZARC_GPU_OK;
+    int rc = 0;
     if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
     NestedCall nested(h);
     std::vector<uint64_t> in_sz(n), out_sz(n), weight(n), flen(n), rlen(n);
@@ -2180,8 +2262,13 @@ int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
         std::vector<uint64_t> foff(m);
         uint64_t fa = 0;
         for (size_t k = 0; k < m; k++) { foff[k] = fa; fa += in_sz[i0 + k]; }
-        rc = zarc_gpu_verify_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
-                                          expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0);
+        if (pattern)
+            rc = zarc_gpu_search_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
+                                              expect ? (const uint8_t *)expect[i0] : nullptr, pattern, pattern_len, flags, (uint8_t *)digest[i0], status + i0,
+                                              count + i0, first + i0);
+        else
+            rc = zarc_gpu_verify_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
+                                              expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0);
         if (helper.joinable()) helper.join();
         if (rc) return rc;
         if (helper_rc) return helper_rc;
@@ -2189,6 +2276,30 @@ int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
     }
     for (int t = 0; t < ZARC_GPU_T_COUNT; t++) h->ms[t] = sum[t];
     return ZARC_GPU_OK;
+}
+} // namespace
+extern "C" {
+
+int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                          const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, 0, 0, nullptr, nullptr);
+}
+
+// verify's chunk loop with the search behind every chunk's verdict: the compressed bytes go up, 52 bytes per frame come back
+int zarc_gpu_search_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                          const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *pattern, size_t pattern_len, unsigned flags,
+                          uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if ((rc = search_check_args(h, pattern, pattern_len, flags, digest, status, count, first))) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if ((rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc;
+    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, pattern, pattern_len, flags, count, first);
 }
 
 

@@ -196,6 +196,12 @@ __global__ void zarc_check_compare(uint32_t n, const uint64_t *slice_prefix, con
 // of frame i); a frame whose status is not OK becomes an entry of no bytes
 __global__ void zarc_repack_plan(uint32_t n, const uint32_t *entry_of, const int32_t *status, const uint64_t *dec_off, const uint64_t *raw_len,
                                  const uint64_t *dec_xxh, uint64_t *src_off /* pack */, uint64_t *src_len /* pack */, uint64_t *xxh /* pack */);
+// search (zdec_search.hip): one byte string of m bytes (1 .. ZARC_SEARCH_MAX_PATTERN; folded by the host when icase) in the decoded bytes of
+// every frame whose status is OK or DIGEST, a workgroup per (frame, slice of ZARC_CHECK_SLICE start positions); every array is in the
+// decoder's order.  count[i] (start: 0) += matching start positions, first[i] (start: 0xFFFFFFFF) = the lowest of them
+constexpr uint32_t ZARC_SEARCH_MAX_PATTERN = 256;
+__global__ void zarc_search_scan(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                 const int32_t *status, const uint8_t *pattern, uint32_t m, uint32_t icase, uint32_t *count, uint32_t *first);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

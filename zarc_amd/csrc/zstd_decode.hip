@@ -2181,3 +2181,5 @@ __global__ void __launch_bounds__(64) zarc_zdec_literals(const uint8_t *__restri
     }
     if (!ok) fast[f] = 0;
 }
+
+#include "zdec_search.hip" // zarc_search_scan: fixed-string search over the decoded bytes of a verify pass

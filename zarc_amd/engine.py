@@ -174,6 +174,27 @@ class Engine:
             dst_len.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return dst_off, dst_len, dig, status
 
+    def search_device(self, d_frames, frame_off, frame_len, raw_len, pattern, icase=False, expect=None):
+        """verify_device plus a search of what was decoded, where it lies: -> list of (status, digest, count, first) per frame.
+        `pattern` is a fixed byte string (host memory, 1..256 bytes); count = matching start positions, first = the lowest or None."""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        count, first = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        pat = bytes(pattern)
+        self._check(self.lib.zarc_gpu_search_batch_device(
+            self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0,
+            dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+            count.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), first.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i])) for i in range(n)]
+
     # ---- host-memory batch calls (the shape of the reference's API: slices in, bytes out) ----
     def blake3(self, entries):
         n = len(entries)
@@ -286,6 +307,27 @@ class Engine:
                                                    exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
                                                    dig.ctypes.data_as(ctypes.c_void_p), status))
         return [(bytes(dig[i]), int(status[i])) for i in range(n)]
+
+    def search(self, frames, raw_lens, pattern, icase=False, expect=None):
+        """-> list of (status, digest, count, first) per frame: verify()'s verdict, the number of start positions at which the fixed byte
+        string `pattern` (1..256 bytes; icase folds ASCII letters only) occurs in the frame's content, and the lowest of them (None without
+        a match).  Only the compressed frames cross to the device; no content comes back."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        count, first = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        pat = bytes(pattern)
+        self._check(self.lib.zarc_gpu_search_batch(self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+                                                   ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0,
+                                                   dig.ctypes.data_as(ctypes.c_void_p), status, count, first))
+        return [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i])) for i in range(n)]
 
     def repack(self, frames, raw_lens, expect=None):
         """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with

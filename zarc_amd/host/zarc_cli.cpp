@@ -182,7 +182,7 @@ bool safe_name(const std::vector<std::string> &name)
 
 int usage()
 {
-    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|list-files> ...\n"
+    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|grep|list-files> ...\n"
                          "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] [--split-blocks] [--check] PATH...\n"
                          "         --split-blocks  cut 64 KiB blocks where their statistics change (smaller frames on binaries / JSON; off by default)\n"
                          "         --check         decode every frame again on the device and compare it with its file before it is written; a mismatch\n"
@@ -195,6 +195,12 @@ int usage()
                          "         encodes every content frame of INPUT again with these flags (pack's), on the device, and carries the directory over;\n"
                          "         --keep-smaller copies a frame unchanged when its new form is not smaller.  A frame that is not good ends the run with\n"
                          "         exit status 1 and nothing is left at PATH\n"
+                         "       zarc grep [-i] [-l] [-b] [--hex] [--filter REGEX]... [--verify DIGEST] [--gpus N] PATTERN ARCHIVE\n"
+                         "         searches the content of the files for PATTERN on the device, each distinct frame once, and writes nothing.  PATTERN is a\n"
+                         "         fixed string of 1 to 256 bytes (grep -F), never a regular expression; --hex reads it as hex digits.  One line per file with\n"
+                         "         a match: PATH:COUNT (overlapping occurrences count); -b adds :OFFSET of the first one, -l prints PATH alone, -i folds ASCII\n"
+                         "         letters.  The matching lines are not printed: unpack the hits with `zarc unpack --filter`.  Exit status as grep's: 0 a\n"
+                         "         match, 1 none, 2 a frame that is not good or any other error\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -722,6 +728,118 @@ int cmd_verify(const std::vector<std::string> &a)
     return failed ? 1 : 0;
 }
 
+// `zarc grep`: which files contain this byte string?  Every distinct content frame behind the files that pass the filters is decoded,
+// judged and searched on the device (zarc_gpu_search_batch): the compressed bytes go up, a few words per frame come back, and a frame
+// that many files share is searched once.  Nothing is created, opened or changed in the file system.  Exit status: grep's.
+int cmd_grep(const std::vector<std::string> &a)
+{
+    std::string pattern, input, verify;
+    std::vector<std::regex> filters;
+    bool icase = false, names_only = false, with_offset = false, hex = false, have_pattern = false, options = true;
+    int gpus = 1;
+    for (size_t i = 0; i < a.size(); i++) {
+        if (options && a[i] == "--filter" && i + 1 < a.size()) filters.emplace_back(a[++i]);
+        else if (options && a[i] == "--verify" && i + 1 < a.size()) verify = a[++i];
+        else if (options && a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str());
+        else if (options && a[i] == "--hex") hex = true;
+        else if (options && a[i] == "--") options = false;
+        else if (options && a[i].size() >= 2 && a[i][0] == '-' && a[i][1] != '-') { // -i -l -b -F, alone or bundled
+            for (size_t k = 1; k < a[i].size(); k++) {
+                if (a[i][k] == 'i') icase = true;
+                else if (a[i][k] == 'l') names_only = true;
+                else if (a[i][k] == 'b') with_offset = true;
+                else if (a[i][k] == 'F') {} // fixed strings are all there is
+                else return usage();
+            }
+        } else if (options && a[i].size() >= 2 && a[i][0] == '-') return usage();
+        else if (!have_pattern) { pattern = a[i]; have_pattern = true; }
+        else if (input.empty()) input = a[i];
+        else return usage();
+    }
+    if (!have_pattern || input.empty() || gpus < 1 || gpus > 64) return usage();
+    if (hex) {
+        std::string raw;
+        if (pattern.size() % 2) { std::fprintf(stderr, "Error: --hex wants an even number of hex digits\n"); return 2; }
+        for (size_t k = 0; k < pattern.size(); k += 2) {
+            if (!std::isxdigit((unsigned char)pattern[k]) || !std::isxdigit((unsigned char)pattern[k + 1])) { std::fprintf(stderr, "Error: --hex wants hex digits\n"); return 2; }
+            raw.push_back((char)std::stoi(pattern.substr(k, 2), nullptr, 16));
+        }
+        pattern = raw;
+    }
+    if (pattern.empty() || pattern.size() > ZARC_GPU_SEARCH_MAX_PATTERN) { std::fprintf(stderr, "Error: the pattern has 1 to %d bytes\n", ZARC_GPU_SEARCH_MAX_PATTERN); return 2; }
+    try {
+        if (gpus > zarc_gpu_device_count()) { std::fprintf(stderr, "Error: --gpus %d but %d device(s) are usable\n", gpus, zarc_gpu_device_count()); return 2; }
+        Mapped m(input);
+        std::vector<int> devices;
+        for (int d = 0; d < gpus; d++) devices.push_back(d);
+        zarc::ArchiveReader rd(m.p, m.n, devices);
+        const std::string digest = base64(rd.trailer().digest.bytes.data(), 32);
+        if (!verify.empty()) {
+            if (verify != digest) { std::fprintf(stderr, "Error: integrity failure: zarc file digest is %s\n", digest.c_str()); return 2; }
+        } else std::fprintf(stderr, "digest: %s\n", digest.c_str());
+        // the files of every distinct frame: a frame is searched ONCE however many files share it
+        std::map<zarc::Digest, std::vector<size_t>> files_of;
+        std::vector<zarc::Digest> order;
+        unsigned long long n_files = 0, failed = 0, bytes = 0, matched = 0;
+        for (size_t i = 0; i < rd.files().size(); i++) {
+            const zarc::File &f = rd.files()[i];
+            if (!f.is_normal() || !passes(filters, to_path(f.name))) continue;
+            n_files++;
+            if (!rd.frames().count(*f.digest)) {
+                std::fprintf(stderr, "WARN frame not found path=%s\n", to_path(f.name).c_str());
+                failed++;
+                continue;
+            }
+            auto &v = files_of[*f.digest];
+            if (v.empty()) order.push_back(*f.digest);
+            v.push_back(i);
+        }
+        // results by file index, printed in directory order once every batch is through
+        struct Hit { uint64_t count; uint64_t first; };
+        std::map<size_t, Hit> hits;
+        const size_t BATCH = (size_t)1 << 30;
+        std::vector<zarc::Digest> batch;
+        size_t batch_bytes = 0;
+        auto flush = [&]() {
+            if (batch.empty()) return;
+            const std::vector<zarc::FrameReader::Result> res = rd.search_frames(batch, pattern, icase);
+            for (size_t k = 0; k < batch.size(); k++) {
+                const bool decoded = res[k].status == ZARC_GPU_FRAME_OK || res[k].status == ZARC_GPU_FRAME_DIGEST;
+                for (size_t i : files_of[batch[k]]) {
+                    const std::string path = to_path(rd.files()[i].name);
+                    if (decoded && res[k].verify.value_or(false)) { if (res[k].count) hits[i] = Hit{res[k].count, res[k].first.value_or(0)}; continue; }
+                    if (decoded) std::fprintf(stderr, "ERROR frame verification failed! path=%s\n", path.c_str()); // verify's wording
+                    else std::fprintf(stderr, "ERROR %s path=%s\n", zarc_gpu_frame_status_name(res[k].status), path.c_str());
+                    failed++;
+                }
+            }
+            LOGF(3, "search_frames", "frames=%zu bytes=%zu", batch.size(), batch_bytes);
+            batch.clear();
+            batch_bytes = 0;
+        };
+        for (const zarc::Digest &d : order) {
+            const uint64_t u = rd.frames().at(d).uncompressed;
+            batch.push_back(d);
+            batch_bytes += (size_t)u;
+            bytes += u;
+            if (batch_bytes >= BATCH) flush();
+        }
+        flush();
+        for (const auto &kv : hits) {
+            const std::string path = to_path(rd.files()[kv.first].name);
+            if (names_only) std::printf("%s\n", path.c_str());
+            else if (with_offset) std::printf("%s:%llu:%llu\n", path.c_str(), (unsigned long long)kv.second.count, (unsigned long long)kv.second.first);
+            else std::printf("%s:%llu\n", path.c_str(), (unsigned long long)kv.second.count);
+            matched++;
+        }
+        std::fprintf(stderr, "searched %llu files (%zu frames, %llu bytes), %llu match, %llu failed\n", n_files, order.size(), bytes, matched, failed);
+        return failed ? 2 : (matched ? 0 : 1);
+    } catch (const zarc::Error &e) {
+        std::fprintf(stderr, "Error: %s\n", e.what());
+        return 2;
+    }
+}
+
 // `zarc repack`: one archive into another.  The content frames are decoded, judged and encoded again on the device
 // (zarc_gpu_repack_batch through ArchiveWriter::repack_from): no file is created but the output, no content crosses PCIe raw, and the
 // directory -- owners, times, links, attributes, whatever this file system could not hold -- is carried over as it is.
@@ -827,7 +945,7 @@ int main(int argc, char **argv)
         else if (a == "--log-file") {
             have_log_file = true;
             // num_args = 0..=1: a following word that is not a subcommand is the path
-            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
+            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0 || std::string("grep").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
         } else break;
     }
     if (i >= argc) return usage();
@@ -841,6 +959,7 @@ int main(int argc, char **argv)
         if (!verb.empty() && std::string("list-files").rfind(verb, 0) == 0) return cmd_list_files(rest);
         if (!verb.empty() && std::string("verify").rfind(verb, 0) == 0) return cmd_verify(rest);
         if (!verb.empty() && std::string("repack").rfind(verb, 0) == 0) return cmd_repack(rest);
+        if (!verb.empty() && std::string("grep").rfind(verb, 0) == 0) return cmd_grep(rest);
         return usage();
     } catch (const zarc::Error &e) {
         std::fprintf(stderr, "Error: %s\n", e.what());

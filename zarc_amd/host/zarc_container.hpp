@@ -434,6 +434,18 @@ class ArchiveReader {
         }
         return reader_.check_content_frames(data_, len_, wanted);
     }
+    // check_frames plus a search of the decoded content on the device (FrameReader::search_content_frames): count and first of ONE fixed
+    // byte string per digest, in order; no content comes back
+    std::vector<FrameReader::Result> search_frames(const std::vector<Digest> &digests, const std::string &pattern, bool icase = false)
+    {
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.search_content_frames(data_, len_, wanted, pattern, icase);
+    }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()
     {

@@ -370,6 +370,8 @@ class FrameReader {
         Digest digest;                   // FrameIterator::digest() once the frame is done
         std::optional<bool> verify;      // FrameIterator::verify(): None if the frame did not decode
         int status = ZARC_GPU_FRAME_OK;  // Error::Zstd analogue (decode/error.rs:35-38) via zarc_gpu_frame_status_name
+        uint64_t count = 0;              // search_content_frames: start positions at which the pattern occurs (0 for a frame that did not decode)
+        std::optional<uint64_t> first;   // ... and the lowest of them
     };
     explicit FrameReader(int device = 0) : FrameReader(std::vector<int>{device}) {}
     explicit FrameReader(const std::vector<int> &devices)
@@ -392,9 +394,20 @@ class FrameReader {
     {
         return run_frames(archive, archive_len, wanted, false);
     }
+    // check_content_frames plus a search of what was decoded, on the device (zarc_gpu_search_batch): {digest, verify, status, count, first}
+    // per frame for ONE fixed byte string of 1 .. ZARC_GPU_SEARCH_MAX_PATTERN bytes; icase folds ASCII letters only.  The same dealing
+    // over the handles, results in the caller's order and identical for every number of handles; no content comes back.
+    std::vector<Result> search_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const std::string &pattern,
+                                              bool icase = false)
+    {
+        if (pattern.empty() || pattern.size() > ZARC_GPU_SEARCH_MAX_PATTERN) throw Error(ZARC_GPU_E_PARAM, "the pattern has 1 to 256 bytes");
+        const Search s{&pattern, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u};
+        return run_frames(archive, archive_len, wanted, false, &s);
+    }
 
   private:
-    std::vector<Result> run_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, bool with_data)
+    struct Search { const std::string *pattern; unsigned flags; };
+    std::vector<Result> run_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, bool with_data, const Search *search = nullptr)
     {
         const size_t n = wanted.size();
         std::vector<Result> out(n);
@@ -417,11 +430,15 @@ class FrameReader {
             std::vector<size_t> fl(m), ul(m);
             std::vector<Digest> expect(m), got(m);
             std::vector<int> status(m);
+            std::vector<uint64_t> count(search ? m : 0), first(search ? m : 0);
             for (size_t j = 0; j < m; j++) {
                 const Frame &f = wanted[idx[j]];
                 fp[j] = archive + f.offset; fl[j] = f.length; ul[j] = f.uncompressed; dp[j] = out[idx[j]].data.data(); expect[j] = f.digest;
             }
-            rc[d] = with_data ? zarc_gpu_unpack_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), dp.data(), (const uint8_t(*)[32])expect.data(),
+            rc[d] = search    ? zarc_gpu_search_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
+                                                      search->pattern->data(), search->pattern->size(), search->flags, (uint8_t(*)[32])got.data(),
+                                                      status.data(), count.data(), first.data())
+                    : with_data ? zarc_gpu_unpack_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), dp.data(), (const uint8_t(*)[32])expect.data(),
                                                       (uint8_t(*)[32])got.data(), status.data())
                               : zarc_gpu_verify_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
                                                       (uint8_t(*)[32])got.data(), status.data());
@@ -433,6 +450,7 @@ class FrameReader {
                 const bool decoded = status[j] == ZARC_GPU_FRAME_OK || status[j] == ZARC_GPU_FRAME_DIGEST;
                 if (decoded) r.verify = got[j] == expect[j]; // a mismatch is reported, not fatal (zarc-cli/src/unpack.rs:118-120)
                 else r.data.clear();
+                if (search) { r.count = count[j]; if (first[j] != ZARC_GPU_SEARCH_NONE) r.first = first[j]; }
             }
         };
         if (g == 1) unpack_share(0);
