@@ -44,7 +44,8 @@ extern "C" {
                                   version (they are new symbols and new ids; nothing older changed): a library from before them fails a caller
                                   that wants them at the symbol lookup, not by version.  zarc_gpu_repack_batch* joined them the same way, for the
                                   same reason, and zarc_gpu_search_batch* with ZARC_GPU_T_SEARCH after them (ZARC_GPU_T_COUNT grew from 10 to 11:
-                                  zarc_gpu_last_kernel_ms of an older library answers < 0 for the new id, as for any id it does not know) */
+                                  zarc_gpu_last_kernel_ms of an older library answers < 0 for the new id, as for any id it does not know), and
+                                  zarc_gpu_search_lines_batch* with ZARC_GPU_T_LINES after those (ZARC_GPU_T_COUNT grew from 11 to 12) */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -312,6 +313,49 @@ int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_b
                                  const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const void *pattern /* HOST pointer */,
                                  size_t pattern_len, unsigned flags, uint8_t *digest /* n*32 */, int *status, uint64_t *count, uint64_t *first);
 
+/* ---- search, lines: the matching lines of a search, gathered on the device ------------------------------------------------------------ */
+/* What `grep -n -F` prints per file: zarc_gpu_search_batch, plus the lines that hold a match.  Only those lines' bytes leave the device.
+ *   - A LINE is a maximal run of content bytes without 0x0A; it is ended by a 0x0A or by the frame's end; the 0x0A is not part of it (a
+ *     0x0D in front of it is).  Content that ends in 0x0A has no extra empty last line; an empty frame has no line.  A line's NUMBER is 1 +
+ *     the count of 0x0A bytes in front of its first byte.  A line MATCHES when at least one matching start position (as
+ *     zarc_gpu_search_batch defines it, ZARC_GPU_SEARCH_ICASE included) lies in it; a line with several matches is one line.
+ *   - The pattern must not contain 0x0A (ZARC_GPU_E_PARAM): a match then never spans two lines.  Nothing crosses a frame's end.
+ *   - status, digest, count, first: EXACTLY what zarc_gpu_search_batch gives for the same arguments.  lines[i] = the number of matching
+ *     lines of frame i, ALL of them whatever the caps.  Frames that did not decode (status other than OK / DIGEST): 0 lines, no record.
+ *   - Delivery, the same for every scratch budget, every chunking, host and device form: go through the frames in batch order; frame i
+ *     delivers its first d_i = min(lines[i], max_lines (0 = no limit), rec_cap - sum of d_j, j < i) matching lines in ascending `start`.
+ *     Records are therefore ordered by (frame, start); *rec_used = the sum of d_i.  A caller sees truncation by comparing with lines[i].
+ *   - text is compact: text_off is the running sum of text_len in record order, *text_used the whole sum.  text_cap < rec_cap * max_line
+ *     (or a product that overflows): ZARC_GPU_E_DSTSIZE -- the text can then never run out on its own.  rec_cap == 0 is a counting call:
+ *     rec and text may be NULL, both *_used are 0.
+ *   - ZARC_GPU_E_PARAM: everything zarc_gpu_search_batch refuses, a missing lines / rec_used / text_used, a NULL rec or text with
+ *     rec_cap > 0, max_line outside 1 .. ZARC_GPU_LINES_MAX_LINE, a 0x0A in the pattern.  n == 0: ZARC_GPU_OK, both *_used 0.  A frame or
+ *     raw length of 4 GiB or more: ZARC_GPU_E_UNSUPPORTED.
+ *   - Host form: `text` is host memory; the frames go up and exactly *text_used bytes of content come back (zarc_gpu_last_copy_bytes:
+ *     H2D = sum of frame_len, D2H = *text_used; records, counts and statuses are descriptors).  Device form: frames and `text` are device
+ *     memory, `rec` and every per-frame array are host arrays; the counters report 0.
+ *   - zarc_gpu_last_kernel_ms: search's timers, ZARC_GPU_T_LINES for the line kernels, ZARC_GPU_T_TOTAL including them. */
+#define ZARC_GPU_LINES_MAX_LINE 65536
+typedef struct {
+    uint64_t frame;    /* index in the batch */
+    uint64_t start;    /* offset of the line's first byte in the frame's content */
+    uint64_t length;   /* the whole line in bytes, without its 0x0A, however long */
+    uint64_t number;   /* 1-based line number */
+    uint64_t match;    /* lowest matching start position in the line (offset in the content) */
+    uint64_t text_off; /* where the delivered bytes lie in `text` */
+    uint64_t text_len; /* min(length, max_line): the line's FIRST text_len bytes */
+} zarc_gpu_line;
+int zarc_gpu_search_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const void *pattern, size_t pattern_len, unsigned flags,
+                                uint64_t max_lines /* per frame; 0 = no limit */, uint64_t max_line /* 1..65536 */,
+                                uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *lines /* n */,
+                                zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *text, size_t text_cap, size_t *text_used);
+int zarc_gpu_search_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                       const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const void *pattern /* HOST pointer */,
+                                       size_t pattern_len, unsigned flags, uint64_t max_lines, uint64_t max_line, uint8_t *digest /* n*32 */,
+                                       int *status, uint64_t *count, uint64_t *first, uint64_t *lines, zarc_gpu_line *rec /* HOST array */,
+                                       size_t rec_cap, size_t *rec_used, void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
+
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN]);
@@ -337,7 +381,8 @@ enum {
     ZARC_GPU_T_DEC_LITS = 8,  /* decoder stage 2: Huffman literals (zarc_zdec_literals, side stream)      */
     ZARC_GPU_T_DEC_FRAMES = 9,/* decoder frame pass (zarc_zstd_frames + the inline decoder for the rest)  */
     ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan, summed over the parts of a call; < 0 or 0 after any other call */
-    ZARC_GPU_T_COUNT = 11
+    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_COUNT = 12
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);
 /* Content bytes the most recent batch call moved between host and device (descriptor arrays, statuses, digests not counted).  Every

@@ -34,15 +34,17 @@ C_H2D, C_D2H, C_RING, C_DIRECT = range(4)
 # timers
 T_BLAKE3, T_XXH64, T_MATCH, T_ENTROPY, T_ASSEMBLE, T_DECODE, T_TOTAL, T_DEC_SEQS, T_DEC_LITS, T_DEC_FRAMES = range(10)
 T_SEARCH = 10  # zarc_search_scan of a search call (summed over its parts)
+T_LINES = 11   # zarc_lines_* of a search_lines call (summed over its parts)
 # zarc_gpu_search_batch*: flags, the longest pattern, first[i] of a frame without a match
 SEARCH_ICASE, SEARCH_MAX_PATTERN, SEARCH_NONE = 1, 256, 2 ** 64 - 1
+LINES_MAX_LINE = 65536  # zarc_gpu_search_lines_batch*: the largest max_line
 
 EXPORTS = [
     "zarc_gpu_abi_version", "zarc_gpu_level_finder", "zarc_gpu_parameter_advisory", "zarc_gpu_device_count", "zarc_gpu_create", "zarc_gpu_destroy", "zarc_gpu_set_parameter", "zarc_gpu_get_params",
     "zarc_gpu_enable_compression", "zarc_gpu_bound", "zarc_gpu_error_name", "zarc_gpu_frame_status_name", "zarc_gpu_last_error",
     "zarc_gpu_pack_batch", "zarc_gpu_pack_batch_device", "zarc_gpu_pack_batch_dedup", "zarc_gpu_pack_batch_device_dedup", "zarc_gpu_unpack_batch", "zarc_gpu_unpack_batch_device",
     "zarc_gpu_verify_batch", "zarc_gpu_verify_batch_device", "zarc_gpu_last_copy_bytes", "zarc_gpu_repack_batch", "zarc_gpu_repack_batch_device",
-    "zarc_gpu_search_batch", "zarc_gpu_search_batch_device",
+    "zarc_gpu_search_batch", "zarc_gpu_search_batch_device", "zarc_gpu_search_lines_batch", "zarc_gpu_search_lines_batch_device",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -55,6 +57,11 @@ KNOWN_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes
 class Params(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("level", "checksum_flag", "content_size_flag", "window_log", "hash_log", "chain_log",
                                             "search_log", "min_match", "target_length", "strategy", "compress")]
+
+
+class Line(ctypes.Structure):
+    """zarc_gpu_line: one matching line of a search_lines call"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("frame", "start", "length", "number", "match", "text_off", "text_len")]
 
 
 class ZarcGpuError(RuntimeError):
@@ -107,6 +114,10 @@ def load(path=None):
     lib.zarc_gpu_repack_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, sz, u64p, u64p, vp, ip]
     lib.zarc_gpu_search_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vp, sz, c.c_uint, vp, ip, u64p, u64p]
     lib.zarc_gpu_search_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, sz, c.c_uint, vp, ip, u64p, u64p]
+    lp = c.POINTER(Line)
+    lib.zarc_gpu_search_lines_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vp, sz, c.c_uint, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, lp, sz, szp, vp, sz, szp]
+    lib.zarc_gpu_search_lines_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, sz, c.c_uint, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, lp, sz,
+                                                       szp, vp, sz, szp]
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

@@ -114,6 +114,10 @@ struct zarc_gpu {
     DevBuf d_rp_order, d_rp_xxh; // zarc_repack_plan: the caller's index of every frame of the decoder's order; XXH64 by entry for frame assembly
     // search (zarc_gpu_search_batch*): zarc_search_scan over d_vout behind the verdict of a verify pass
     DevBuf d_srch_pat, d_srch_slices, d_srch_count, d_srch_first; // the (folded) pattern; slice prefix, matches and lowest match of every frame (decoder order)
+    // the matching lines of a search (zarc_gpu_search_lines_batch*): zarc_lines_* behind zarc_search_scan, per part
+    DevBuf d_ln_slices, d_ln_lines;             // ZarcLineSlice of every slice; matching lines of every frame (decoder order)
+    DevBuf d_ln_base, d_ln_deliver;             // what the host decided: first record and number of records of every frame (decoder order)
+    DevBuf d_ln_rec, d_ln_total, d_ln_text;     // the part's records, the sum of their text_len, and (host form) their text: sized by what the part delivers
     bool vout_busy = false;     // a repack pass is between its halves: d_vout is not the check's to take
     uint64_t dec_scratch = 0;   // decoder scratch (sequences, literals, tables) of the most recent decode, as counted against the budget
     // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
@@ -623,11 +627,29 @@ struct PackPlanned {
 
 // A verify pass that also searches what it decoded (zarc_gpu_search_batch*): zarc_search_scan runs behind the verdict, per part, while that
 // part's bytes are in d_vout
+// ... and gathers the matching lines (zarc_gpu_search_lines_batch*).  The parts of a call -- chunks of the host form, halves of
+// unpack_device_split -- are contiguous ranges of the caller's frames processed in the caller's order, so the running remainder of rec_cap in
+// `run` gives every frame the same records however the call is cut.
+struct LinesRun { size_t rec_used = 0; uint64_t text_used = 0; float ms = 0; }; // one per call
+struct LinesReq {
+    uint64_t max_lines;        // per frame; 0 = no limit
+    uint32_t max_line;
+    uint64_t *lines;           // host, in the caller's order, this part's first frame first
+    uint64_t frame0;           // the caller's index of this part's first frame
+    zarc_gpu_line *rec;        // host: the call's records
+    size_t rec_cap;
+    uint8_t *d_text;           // device form: the caller's text buffer
+    uint8_t *h_text;           // host form: the caller's text buffer (the part's text is gathered into scratch of the handle first)
+    LinesRun *run;
+};
 struct SearchReq {
     const uint8_t *d_pattern;  // device: the pattern, folded when icase
     uint32_t m, icase;
     uint64_t *count, *first;   // host, in the caller's order: matching start positions; the lowest, or ZARC_GPU_SEARCH_NONE
+    const LinesReq *ln = nullptr;
 };
+int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
+static_assert(sizeof(ZarcLineRec) == sizeof(zarc_gpu_line), "the device's record is the caller's");
 
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, void *d_dst_base,
                         const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk,
@@ -1497,12 +1519,15 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
                        h->d_stored_ck.as<uint32_t>(), h->d_digests.as<uint32_t>(), expect_in ? h->d_expect.as<uint32_t>() : (const uint32_t *)nullptr,
                        h->d_status.as<int32_t>());
     ZHIP(hipGetLastError());
-    int e5 = -1, e6 = -1;
+    int e5 = -1, e6 = -1, e7 = -1;
+    uint64_t slices_total = 0;
+    float lines_ms2 = 0;
     if (srch) { // ---- search: the decoded bytes are judged; look through those of the frames that decoded, where they lie
         std::vector<uint64_t> slices(n + 1, 0);
         for (size_t i = 0; i < n; i++) slices[i + 1] = slices[i] + std::max<uint64_t>(1, (raw_len[i] + ZARC_CHECK_SLICE - 1) / ZARC_CHECK_SLICE);
         if (slices[n] > 0x7FFFFFFFull) { set_error(h, "search: batch too large"); return ZARC_GPU_E_PARAM; }
         if ((rc = upload_u64(h, h->d_srch_slices, slices.data(), n + 1))) return rc;
+        slices_total = slices[n];
         ZHIP(h->d_srch_count.reserve(n * 4));
         ZHIP(h->d_srch_first.reserve(n * 4));
         ZHIP(hipMemsetAsync(h->d_srch_count.p, 0, n * 4, h->stream));
@@ -1513,6 +1538,17 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
                            h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>());
         ZHIP(hipGetLastError());
         ZHIP(t.mark(&e6));
+        if (srch->ln) { // ---- lines, first half: what every slice holds, what every slice must know of its neighbours, lines[] of every frame
+            ZHIP(h->d_ln_slices.reserve(slices[n] * sizeof(ZarcLineSlice)));
+            ZHIP(h->d_ln_lines.reserve(n * 4));
+            hipLaunchKernelGGL(zarc_lines_mark, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_pattern, srch->m, srch->icase,
+                               h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
+            hipLaunchKernelGGL(zarc_lines_carry, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(),
+                               h->d_raw_len.as<uint64_t>(), h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
+            ZHIP(hipGetLastError());
+            ZHIP(t.mark(&e7));
+        }
     }
     std::vector<int32_t> st_v;
     std::vector<uint8_t> dg_v;
@@ -1528,9 +1564,64 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         ZHIP(hipMemcpyAsync(sc.data(), h->d_srch_count.p, n * 4, hipMemcpyDeviceToHost, h->stream));
         ZHIP(hipMemcpyAsync(sf.data(), h->d_srch_first.p, n * 4, hipMemcpyDeviceToHost, h->stream));
     }
+    std::vector<uint32_t> ln_lines;
+    if (srch && srch->ln) { ln_lines.resize(n); ZHIP(hipMemcpyAsync(ln_lines.data(), h->d_ln_lines.p, n * 4, hipMemcpyDeviceToHost, h->stream)); }
     ZHIP(hipStreamSynchronize(h->stream));
     for (size_t i = 0; i < n; i++) { status[order[i]] = st[i]; memcpy(digest + (size_t)order[i] * 32, dg + i * 32, 32); }
     if (srch) for (size_t i = 0; i < n; i++) { srch->count[order[i]] = sc[i]; srch->first[order[i]] = sf[i] == 0xFFFFFFFFu ? ZARC_GPU_SEARCH_NONE : sf[i]; }
+    if (srch && srch->ln) { // ---- lines, second half: the delivery rule in the caller's order, then records and text of what this part delivers
+        const LinesReq &ln = *srch->ln;
+        LinesRun &run = *ln.run;
+        std::vector<uint32_t> where(n); // the decoder's index of the caller's frame
+        for (size_t i = 0; i < n; i++) where[order[i]] = (uint32_t)i;
+        std::vector<uint64_t> base(n);
+        std::vector<uint32_t> deliver(n);
+        uint64_t nrec = 0;
+        for (size_t c = 0; c < n; c++) {
+            const uint32_t i = where[c];
+            ln.lines[c] = ln_lines[i];
+            uint64_t d = ln_lines[i];
+            if (ln.max_lines && d > ln.max_lines) d = ln.max_lines;
+            d = std::min<uint64_t>(d, ln.rec_cap - run.rec_used - nrec);
+            base[i] = nrec; deliver[i] = (uint32_t)d;
+            nrec += d;
+        }
+        if (nrec) {
+            if ((rc = upload_u64(h, h->d_ln_base, base.data(), n))) return rc;
+            if ((rc = upload_u32(h, h->d_ln_deliver, deliver.data(), n))) return rc;
+            ZHIP(h->d_ln_rec.reserve(nrec * sizeof(ZarcLineRec)));
+            ZHIP(h->d_ln_total.reserve(8));
+            ZHIP(hipMemsetAsync(h->d_ln_rec.p, 0, nrec * sizeof(ZarcLineRec), h->stream)); // (a record nobody wrote would name no frame and no text)
+            int e8, e9;
+            ZHIP(t.mark(&e8));
+            hipLaunchKernelGGL(zarc_lines_emit, dim3((unsigned)slices_total), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), srch->d_pattern, srch->m, srch->icase, h->d_ln_slices.as<ZarcLineSlice>(),
+                               h->d_ln_base.as<uint64_t>(), h->d_ln_deliver.as<uint32_t>(), ln.max_line, h->d_ln_rec.as<ZarcLineRec>());
+            hipLaunchKernelGGL(zarc_lines_scan, dim3(1), dim3(256), 0, h->stream, nrec, h->d_ln_rec.as<ZarcLineRec>(), h->d_ln_total.as<uint64_t>());
+            ZHIP(hipGetLastError());
+            uint64_t text_bytes = 0;
+            std::vector<ZarcLineRec> recs(nrec);
+            ZHIP(hipMemcpyAsync(recs.data(), h->d_ln_rec.p, nrec * sizeof(ZarcLineRec), hipMemcpyDeviceToHost, h->stream));
+            ZHIP(hipMemcpyAsync(&text_bytes, h->d_ln_total.p, 8, hipMemcpyDeviceToHost, h->stream));
+            ZHIP(hipStreamSynchronize(h->stream));
+            uint8_t *d_text = ln.d_text ? ln.d_text + run.text_used : nullptr;
+            if (!d_text) { ZHIP(h->d_ln_text.reserve(text_bytes + 16)); d_text = h->d_ln_text.as<uint8_t>(); } // (host form: sized by what came of the scan)
+            hipLaunchKernelGGL(zarc_lines_gather, dim3((unsigned)((nrec + 3) / 4)), dim3(256), 0, h->stream, nrec, h->d_ln_rec.as<ZarcLineRec>(), (const uint8_t *)d_dst_base,
+                               b_dst_off.as<uint64_t>(), d_text);
+            ZHIP(hipGetLastError());
+            ZHIP(t.mark(&e9));
+            if (ln.h_text && text_bytes && (rc = lines_text_out(h, ln.h_text + run.text_used, d_text, text_bytes))) return rc;
+            ZHIP(hipStreamSynchronize(h->stream));
+            for (uint64_t k = 0; k < nrec; k++) {
+                zarc_gpu_line &r = ln.rec[run.rec_used + k];
+                memcpy(&r, &recs[k], sizeof r);
+                r.frame = ln.frame0 + order[recs[k].frame];
+                r.text_off += run.text_used;
+            }
+            run.rec_used += nrec; run.text_used += text_bytes;
+            lines_ms2 = elapsed(h, e8, e9);
+        }
+    }
     if (fastpath && diag_env("ZARC_GPU_DEC_STATS", 0)) { // diagnostics: how many frames had their sequences decoded ahead
         std::vector<uint32_t> fl(n);
         ZHIP(hipMemcpy(fl.data(), h->d_fast.p, n * 4, hipMemcpyDeviceToHost));
@@ -1564,6 +1655,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     h->ms[ZARC_GPU_T_BLAKE3] = t_b3;
     h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e3);
     if (srch) { h->ms[ZARC_GPU_T_SEARCH] = elapsed(h, e5, e6); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e6); }
+    if (srch && srch->ln) { h->ms[ZARC_GPU_T_LINES] = elapsed(h, e6, e7) + lines_ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e7) + lines_ms2; }
     return ZARC_GPU_OK;
 }
 
@@ -1614,7 +1706,9 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
         PackCheck sub{};
         if (chk) { sub = *chk; sub.first_bad += a; if (chk->entry_map) sub.entry_map += a; else sub.entry0 += (uint32_t)a; }
         SearchReq ssub{};
+        LinesReq lsub{};
         if (srch) { ssub = *srch; ssub.count += a; ssub.first += a; }
+        if (srch && srch->ln) { lsub = *srch->ln; lsub.lines += a; lsub.frame0 += a; ssub.ln = &lsub; }
         rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
                                  digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr);
         if (rc) return rc;
@@ -1688,6 +1782,54 @@ int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_b
     if (!h->nested && (rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc; // (the host form has done it for all its chunks)
     const SearchReq srch{h->d_srch_pat.as<uint8_t>(), (uint32_t)pattern_len, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
     return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
+}
+} // extern "C"
+namespace {
+// what the lines entry points check on top of search_check_args; -> 0, ZARC_GPU_E_PARAM or ZARC_GPU_E_DSTSIZE
+int lines_check_args(zarc_gpu_t *h, const void *pattern, size_t pattern_len, uint64_t max_line, const uint64_t *lines, const zarc_gpu_line *rec, size_t rec_cap,
+                     const size_t *rec_used, const void *text, size_t text_cap, const size_t *text_used)
+{
+    if (!lines || !rec_used || !text_used) return ZARC_GPU_E_PARAM;
+    if (rec_cap && (!rec || !text)) return ZARC_GPU_E_PARAM;
+    if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) { set_error(h, "search_lines: max_line is 1 to 65536"); return ZARC_GPU_E_PARAM; }
+    if (memchr(pattern, 0x0A, pattern_len)) { set_error(h, "search_lines: the pattern must not contain a newline"); return ZARC_GPU_E_PARAM; }
+    if (rec_cap > SIZE_MAX / (size_t)max_line || text_cap < rec_cap * (size_t)max_line) { set_error(h, "search_lines: text_cap is below rec_cap * max_line"); return ZARC_GPU_E_DSTSIZE; }
+    return 0;
+}
+// one part of a lines call (the whole of the device form, a chunk of the host form): search's pass with the line kernels behind it
+int search_lines_part(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, const uint64_t *raw_len,
+                      const uint8_t *expect, size_t pattern_len, unsigned flags, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, const LinesReq &ln)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    SearchReq srch{h->d_srch_pat.as<uint8_t>(), (uint32_t)pattern_len, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
+    srch.ln = &ln;
+    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
+}
+} // namespace
+extern "C" {
+
+// zarc_gpu_search_batch_device with zarc_lines_* behind the search kernel of every part
+int zarc_gpu_search_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                       const uint64_t *raw_len, const uint8_t *expect, const void *pattern, size_t pattern_len, unsigned flags,
+                                       uint64_t max_lines, uint64_t max_line, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, uint64_t *lines,
+                                       zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *d_text, size_t text_cap, size_t *text_used)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if ((rc = search_check_args(h, pattern, pattern_len, flags, digest, status, count, first))) return rc;
+    if ((rc = lines_check_args(h, pattern, pattern_len, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used))) return rc;
+    *rec_used = 0; *text_used = 0;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
+    for (size_t i = 0; i < n; i++)
+        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
+    if ((rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc;
+    LinesRun run;
+    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, (uint8_t *)d_text, nullptr, &run};
+    rc = search_lines_part(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, pattern_len, flags, digest, status, count, first, ln);
+    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
+    return rc;
 }
 
 
@@ -1969,6 +2111,13 @@ int staged_d2h(zarc_gpu *h, hipStream_t stream, const std::vector<Seg> &segs, co
     return 0;
 }
 
+// the text of a part's matching lines, device -> the caller's host buffer (content: counted)
+int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes)
+{
+    const std::vector<Seg> segs{Seg{host, 0, bytes}};
+    return staged_d2h(h, h->stream, segs, dev, bytes);
+}
+
 struct Chunk { size_t i0, i1; uint64_t in_bytes, out_bytes; };
 
 // cut [0, n) into chunks of about STAGE_CHUNK content bytes (at least one entry each)
@@ -2218,7 +2367,7 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 namespace {
 int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                      const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const void *pattern,
-                     size_t pattern_len, unsigned flags, uint64_t *count, uint64_t *first)
+                     size_t pattern_len, unsigned flags, uint64_t *count, uint64_t *first, const LinesReq *ln = nullptr)
 {
     int rc = 0;
     if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
@@ -2262,7 +2411,12 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
         std::vector<uint64_t> foff(m);
         uint64_t fa = 0;
         for (size_t k = 0; k < m; k++) { foff[k] = fa; fa += in_sz[i0 + k]; }
-        if (pattern)
+        if (ln) { // (the chunks are ranges of the caller's frames in the caller's order: the running remainder of rec_cap goes from one to the next)
+            LinesReq sub = *ln;
+            sub.lines += i0; sub.frame0 += i0;
+            rc = search_lines_part(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0, expect ? (const uint8_t *)expect[i0] : nullptr,
+                                   pattern_len, flags, (uint8_t *)digest[i0], status + i0, count + i0, first + i0, sub);
+        } else if (pattern)
             rc = zarc_gpu_search_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
                                               expect ? (const uint8_t *)expect[i0] : nullptr, pattern, pattern_len, flags, (uint8_t *)digest[i0], status + i0,
                                               count + i0, first + i0);
@@ -2300,6 +2454,25 @@ int zarc_gpu_search_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
     if (n == 0) return ZARC_GPU_OK;
     if ((rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc;
     return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, pattern, pattern_len, flags, count, first);
+}
+// search's chunk loop with the line kernels behind every chunk's search: the compressed bytes go up, the matching lines' bytes come back
+int zarc_gpu_search_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *pattern, size_t pattern_len, unsigned flags, uint64_t max_lines,
+                                uint64_t max_line, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *lines,
+                                zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *text, size_t text_cap, size_t *text_used)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if ((rc = search_check_args(h, pattern, pattern_len, flags, digest, status, count, first))) return rc;
+    if ((rc = lines_check_args(h, pattern, pattern_len, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used))) return rc;
+    *rec_used = 0; *text_used = 0;
+    if (n == 0) return ZARC_GPU_OK;
+    if ((rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc;
+    LinesRun run;
+    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, nullptr, (uint8_t *)text, &run};
+    rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, pattern, pattern_len, flags, count, first, &ln);
+    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
+    return rc;
 }
 
 

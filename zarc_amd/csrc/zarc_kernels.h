@@ -202,6 +202,28 @@ __global__ void zarc_repack_plan(uint32_t n, const uint32_t *entry_of, const int
 constexpr uint32_t ZARC_SEARCH_MAX_PATTERN = 256;
 __global__ void zarc_search_scan(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
                                  const int32_t *status, const uint8_t *pattern, uint32_t m, uint32_t icase, uint32_t *count, uint32_t *first);
+// the matching lines of a search (zdec_lines.hip), on the grid of zarc_search_scan; every per-frame array is in the decoder's order.
+// ZarcLineSlice: what zarc_lines_mark finds in a slice (positions count from the slice's first byte) and what zarc_lines_carry adds of the
+// slices around it (positions count from the frame's first byte)
+struct ZarcLineSlice {
+    uint32_t nl_count, first_nl, last_nl; // mark: 0x0A bytes of the slice, the first and the last one
+    uint32_t nlow;                        // mark: lines that begin behind the slice's first 0x0A and have their lowest match in the slice
+    uint32_t flags;                       // mark: 1 = a match in front of the first 0x0A, 2 = behind the last (no 0x0A: anywhere); carry: 4 = the
+                                          // line open at the slice's start holds a match in an earlier slice
+    uint32_t open_start, nl_base, excl;   // carry: where that line starts; 0x0A bytes and matching lines of the frame in front of the slice
+    uint32_t next_end;                    // carry: the first 0x0A behind the slice, or the frame's length
+    uint32_t pad;
+};
+struct ZarcLineRec { uint64_t frame, start, length, number, match, text_off, text_len; }; // zarc_gpu_line; frame: the decoder's index
+__global__ void zarc_lines_mark(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                const int32_t *status, const uint8_t *pattern, uint32_t m, uint32_t icase, ZarcLineSlice *slices, uint32_t *lines);
+__global__ void zarc_lines_carry(uint32_t n, const uint64_t *slice_prefix, const uint64_t *raw_len, ZarcLineSlice *slices, uint32_t *lines);
+// rec_base[i] / deliver[i]: where frame i's records begin in rec[] and how many of its first matching lines get one
+__global__ void zarc_lines_emit(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                const uint8_t *pattern, uint32_t m, uint32_t icase, const ZarcLineSlice *slices, const uint64_t *rec_base,
+                                const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
+__global__ void zarc_lines_scan(uint64_t nrec, ZarcLineRec *rec, uint64_t *total);
+__global__ void zarc_lines_gather(uint64_t nrec, const ZarcLineRec *rec, const uint8_t *dec_base, const uint64_t *dec_off, uint8_t *text);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

@@ -2183,3 +2183,4 @@ __global__ void __launch_bounds__(64) zarc_zdec_literals(const uint8_t *__restri
 }
 
 #include "zdec_search.hip" // zarc_search_scan: fixed-string search over the decoded bytes of a verify pass
+#include "zdec_lines.hip"  // zarc_lines_*: the matching lines of a search, gathered from the decoded bytes

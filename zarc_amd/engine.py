@@ -195,6 +195,42 @@ class Engine:
             count.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), first.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i])) for i in range(n)]
 
+    def search_lines_device(self, d_frames, frame_off, frame_len, raw_len, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+        """search_device plus the matching lines: -> (results, records) as search_lines() gives them.  The text is gathered into a device
+        buffer of rec_cap * max_line bytes and copied back from there."""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        count, first, lines = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        pat = bytes(pattern)
+        rec = (_lib.Line * max(rec_cap, 1))()
+        rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
+        text_cap = rec_cap * max_line
+        d_text = self.malloc(max(text_cap, 1))
+        try:
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            self._check(self.lib.zarc_gpu_search_lines_batch_device(
+                self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+                ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0, max_lines, max_line,
+                dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), count.ctypes.data_as(u64p), first.ctypes.data_as(u64p),
+                lines.ctypes.data_as(u64p), rec, rec_cap, ctypes.byref(rec_used), ctypes.c_void_p(d_text), text_cap, ctypes.byref(text_used)))
+            text = bytes(self.d2h(d_text, text_used.value)) if text_used.value else b""
+        finally:
+            self.free(d_text)
+        return self._lines_result(n, status, dig, count, first, lines, rec, rec_used.value, text)
+
+    @staticmethod
+    def _lines_result(n, status, dig, count, first, lines, rec, rec_used, text):
+        results = [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i]), int(lines[i])) for i in range(n)]
+        records = [(r.frame, r.start, r.length, r.number, r.match, text[r.text_off:r.text_off + r.text_len]) for r in rec[:rec_used]]
+        return results, records
+
     # ---- host-memory batch calls (the shape of the reference's API: slices in, bytes out) ----
     def blake3(self, entries):
         n = len(entries)
@@ -328,6 +364,35 @@ class Engine:
                                                    ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0,
                                                    dig.ctypes.data_as(ctypes.c_void_p), status, count, first))
         return [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i])) for i in range(n)]
+
+    def search_lines(self, frames, raw_lens, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+        """search() plus the lines that hold a match -> (results, records).  results[i] = (status, digest, count, first, lines): search()'s
+        answer and the number of matching lines of frame i (all of them, whatever the caps).  records = [(frame, start, length, number,
+        match, text_bytes)] ordered by (frame, start): per frame the first min(lines, max_lines or all) matching lines while rec_cap
+        lasts; a line is a run of bytes without 0x0A, text_bytes its first min(length, max_line) bytes.  The pattern must not contain
+        0x0A.  Only the compressed frames cross to the device and only the delivered lines' bytes come back."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        count, first, lines = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        pat = bytes(pattern)
+        rec = (_lib.Line * max(rec_cap, 1))()
+        rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
+        text_cap = rec_cap * max_line
+        text = np.empty(max(text_cap, 1), dtype=np.uint8)
+        self._check(self.lib.zarc_gpu_search_lines_batch(
+            self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0, max_lines, max_line,
+            dig.ctypes.data_as(ctypes.c_void_p), status, count, first, lines, rec, rec_cap, ctypes.byref(rec_used),
+            text.ctypes.data_as(ctypes.c_void_p), text_cap, ctypes.byref(text_used)))
+        return self._lines_result(n, status, dig, count, first, lines, rec, rec_used.value, bytes(text[:text_used.value]))
 
     def repack(self, frames, raw_lens, expect=None):
         """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with

@@ -195,12 +195,18 @@ int usage()
                          "         encodes every content frame of INPUT again with these flags (pack's), on the device, and carries the directory over;\n"
                          "         --keep-smaller copies a frame unchanged when its new form is not smaller.  A frame that is not good ends the run with\n"
                          "         exit status 1 and nothing is left at PATH\n"
-                         "       zarc grep [-i] [-l] [-b] [--hex] [--filter REGEX]... [--verify DIGEST] [--gpus N] PATTERN ARCHIVE\n"
+                         "       zarc grep [-i] [-l] [-b] [--hex] [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
+                         "                 [--lines] [-n] [-c] [-a] [-m NUM] [--max-line BYTES] [--batch-lines N] PATTERN ARCHIVE\n"
                          "         searches the content of the files for PATTERN on the device, each distinct frame once, and writes nothing.  PATTERN is a\n"
                          "         fixed string of 1 to 256 bytes (grep -F), never a regular expression; --hex reads it as hex digits.  One line per file with\n"
                          "         a match: PATH:COUNT (overlapping occurrences count); -b adds :OFFSET of the first one, -l prints PATH alone, -i folds ASCII\n"
-                         "         letters.  The matching lines are not printed: unpack the hits with `zarc unpack --filter`.  Exit status as grep's: 0 a\n"
-                         "         match, 1 none, 2 a frame that is not good or any other error\n"
+                         "         letters.  Exit status as grep's: 0 a match, 1 none, 2 a frame that is not good or any other error.\n"
+                         "         --lines, -n, -c, -a, -m, --max-line or --batch-lines select lines mode: the matching lines are gathered on the device and\n"
+                         "         printed as PATH:LINE; -n adds NUMBER: and -b the line's byte OFFSET: in front of LINE, -c prints PATH:NLINES (matching lines)\n"
+                         "         instead, -m NUM stops after NUM lines per file, -l prints PATH alone.  A file with a NUL byte in a line to print gives\n"
+                         "         `Binary file PATH matches` unless -a is given.  A line prints its first --max-line bytes (default 4096, 1 to 65536).\n"
+                         "         --batch-lines N (default 1048576) is the number of lines one device call can bring back; what did not fit is searched again.\n"
+                         "         PATTERN must not contain a newline in lines mode\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -736,9 +742,15 @@ int cmd_grep(const std::vector<std::string> &a)
     std::string pattern, input, verify;
     std::vector<std::regex> filters;
     bool icase = false, names_only = false, with_offset = false, hex = false, have_pattern = false, options = true;
+    bool lines_mode = false, numbers = false, count_lines = false, as_text = false; // lines mode (any of its flags selects it)
+    long long max_per_file = 0, max_line = 4096, batch_lines = 1048576;
     int gpus = 1;
     for (size_t i = 0; i < a.size(); i++) {
         if (options && a[i] == "--filter" && i + 1 < a.size()) filters.emplace_back(a[++i]);
+        else if (options && a[i] == "--lines") lines_mode = true;
+        else if (options && a[i] == "-m" && i + 1 < a.size()) { max_per_file = std::atoll(a[++i].c_str()); lines_mode = true; if (max_per_file < 1) return usage(); }
+        else if (options && a[i] == "--max-line" && i + 1 < a.size()) { max_line = std::atoll(a[++i].c_str()); lines_mode = true; if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) return usage(); }
+        else if (options && a[i] == "--batch-lines" && i + 1 < a.size()) { batch_lines = std::atoll(a[++i].c_str()); lines_mode = true; if (batch_lines < 1) return usage(); }
         else if (options && a[i] == "--verify" && i + 1 < a.size()) verify = a[++i];
         else if (options && a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str());
         else if (options && a[i] == "--hex") hex = true;
@@ -749,6 +761,9 @@ int cmd_grep(const std::vector<std::string> &a)
                 else if (a[i][k] == 'l') names_only = true;
                 else if (a[i][k] == 'b') with_offset = true;
                 else if (a[i][k] == 'F') {} // fixed strings are all there is
+                else if (a[i][k] == 'n') numbers = lines_mode = true;
+                else if (a[i][k] == 'c') count_lines = lines_mode = true;
+                else if (a[i][k] == 'a') as_text = lines_mode = true;
                 else return usage();
             }
         } else if (options && a[i].size() >= 2 && a[i][0] == '-') return usage();
@@ -767,6 +782,7 @@ int cmd_grep(const std::vector<std::string> &a)
         pattern = raw;
     }
     if (pattern.empty() || pattern.size() > ZARC_GPU_SEARCH_MAX_PATTERN) { std::fprintf(stderr, "Error: the pattern has 1 to %d bytes\n", ZARC_GPU_SEARCH_MAX_PATTERN); return 2; }
+    if (lines_mode && pattern.find('\n') != std::string::npos) { std::fprintf(stderr, "Error: the pattern must not contain a newline when lines are asked for\n"); return 2; }
     try {
         if (gpus > zarc_gpu_device_count()) { std::fprintf(stderr, "Error: --gpus %d but %d device(s) are usable\n", gpus, zarc_gpu_device_count()); return 2; }
         Mapped m(input);
@@ -793,6 +809,67 @@ int cmd_grep(const std::vector<std::string> &a)
             auto &v = files_of[*f.digest];
             if (v.empty()) order.push_back(*f.digest);
             v.push_back(i);
+        }
+        if (lines_mode) {
+            // ---- lines mode: the matching lines of every distinct frame (zarc_gpu_search_lines_batch), printed per file in directory order.
+            // -c and -l need no line: a counting call.  Otherwise one call brings back at most --batch-lines lines; frames behind the one
+            // at which they ran out are searched again in a following call, and a frame that is first in its call and still has more
+            // than fit prints what it got and says so.
+            const bool need_lines = !count_lines && !names_only;
+            std::map<zarc::Digest, zarc::FrameReader::Result> done;
+            const size_t BATCH = (size_t)1 << 30;
+            size_t at = 0;
+            std::vector<zarc::Digest> todo = order;
+            for (const zarc::Digest &d : order) bytes += rd.frames().at(d).uncompressed;
+            while (at < todo.size()) {
+                std::vector<zarc::Digest> batch;
+                for (size_t batch_bytes = 0; at + batch.size() < todo.size() && batch_bytes < BATCH; batch_bytes += (size_t)rd.frames().at(batch.back()).uncompressed)
+                    batch.push_back(todo[at + batch.size()]);
+                std::vector<zarc::FrameReader::Result> res =
+                    rd.search_lines(batch, pattern, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0);
+                LOGF(3, "search_lines", "frames=%zu", batch.size());
+                size_t taken = batch.size();
+                for (size_t k = 0; k < batch.size(); k++) {
+                    const uint64_t want = need_lines ? (max_per_file ? std::min<uint64_t>(res[k].lines, (uint64_t)max_per_file) : res[k].lines) : 0;
+                    if (k > 0 && res[k].line_records.size() < want) { taken = k; break; } // the call's records ran out here: this frame and the rest again
+                    done[batch[k]] = std::move(res[k]);
+                }
+                at += taken;
+            }
+            for (size_t i = 0; i < rd.files().size(); i++) {
+                const zarc::File &f = rd.files()[i];
+                if (!f.is_normal() || !passes(filters, to_path(f.name)) || !done.count(*f.digest)) continue;
+                const zarc::FrameReader::Result &r = done.at(*f.digest);
+                const std::string path = to_path(f.name);
+                const bool decoded = r.status == ZARC_GPU_FRAME_OK || r.status == ZARC_GPU_FRAME_DIGEST;
+                if (!(decoded && r.verify.value_or(false))) {
+                    if (decoded) std::fprintf(stderr, "ERROR frame verification failed! path=%s\n", path.c_str());
+                    else std::fprintf(stderr, "ERROR %s path=%s\n", zarc_gpu_frame_status_name(r.status), path.c_str());
+                    failed++;
+                    continue;
+                }
+                if (!r.lines) continue;
+                matched++;
+                const uint64_t shown = max_per_file ? std::min<uint64_t>(r.lines, (uint64_t)max_per_file) : r.lines;
+                if (names_only) { std::printf("%s\n", path.c_str()); continue; }
+                if (count_lines) { std::printf("%s:%llu\n", path.c_str(), (unsigned long long)shown); continue; }
+                bool binary = false;
+                if (!as_text) for (const auto &l : r.line_records) binary = binary || std::memchr(l.text.data(), 0, l.text.size()) != nullptr;
+                if (binary) { std::printf("Binary file %s matches\n", path.c_str()); continue; }
+                for (const auto &l : r.line_records) {
+                    std::printf("%s:", path.c_str());
+                    if (numbers) std::printf("%llu:", (unsigned long long)l.number);
+                    if (with_offset) std::printf("%llu:", (unsigned long long)l.start);
+                    std::fwrite(l.text.data(), 1, l.text.size(), stdout);
+                    std::fputc('\n', stdout);
+                    if (l.length > l.text.size())
+                        std::fprintf(stderr, "WARN line cut path=%s line=%llu length=%llu\n", path.c_str(), (unsigned long long)l.number, (unsigned long long)l.length);
+                }
+                if (r.line_records.size() < shown)
+                    std::fprintf(stderr, "WARN path=%s: %llu more matching lines not shown\n", path.c_str(), (unsigned long long)(shown - r.line_records.size()));
+            }
+            std::fprintf(stderr, "searched %llu files (%zu frames, %llu bytes), %llu match, %llu failed\n", n_files, order.size(), bytes, matched, failed);
+            return failed ? 2 : (matched ? 0 : 1);
         }
         // results by file index, printed in directory order once every batch is through
         struct Hit { uint64_t count; uint64_t first; };

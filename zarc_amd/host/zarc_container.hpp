@@ -446,6 +446,19 @@ class ArchiveReader {
         }
         return reader_.search_content_frames(data_, len_, wanted, pattern, icase);
     }
+    // search_frames plus the matching lines of every frame (FrameReader::lines_content_frames): per digest, in order, `lines` and the
+    // records the delivery rule gives it; only the delivered lines' bytes come back
+    std::vector<FrameReader::Result> search_lines(const std::vector<Digest> &digests, const std::string &pattern, bool icase = false, uint64_t max_lines = 0,
+                                                  uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20)
+    {
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.lines_content_frames(data_, len_, wanted, pattern, icase, max_lines, max_line, rec_cap);
+    }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()
     {

@@ -25,6 +25,7 @@
 // archive is byte-identical to the single-device one.
 #pragma once
 #include "../../include/zarc_gpu.h"
+#include <cstdlib>
 #include <algorithm>
 #include <array>
 #include <cstdint>
@@ -372,6 +373,10 @@ class FrameReader {
         int status = ZARC_GPU_FRAME_OK;  // Error::Zstd analogue (decode/error.rs:35-38) via zarc_gpu_frame_status_name
         uint64_t count = 0;              // search_content_frames: start positions at which the pattern occurs (0 for a frame that did not decode)
         std::optional<uint64_t> first;   // ... and the lowest of them
+        // lines_content_frames: the frame's matching lines, all of them counted, and the records of those that were delivered (they own their bytes)
+        struct Line { uint64_t start, length, number, match; std::vector<uint8_t> text; }; // zarc_gpu_line; text: the line's first min(length, max_line) bytes
+        uint64_t lines = 0;
+        std::vector<Line> line_records;
     };
     explicit FrameReader(int device = 0) : FrameReader(std::vector<int>{device}) {}
     explicit FrameReader(const std::vector<int> &devices)
@@ -405,8 +410,29 @@ class FrameReader {
         return run_frames(archive, archive_len, wanted, false, &s);
     }
 
+    // search_content_frames plus the matching lines, gathered on the device (zarc_gpu_search_lines_batch): `lines` of every frame and the
+    // records the delivery rule gives it -- frames in the caller's order, per frame the first min(lines, max_lines or all, what rec_cap
+    // leaves) matching lines.  Every handle runs its share with the caller's caps, the shares are merged in the caller's order and the rule
+    // is applied once more on the merged list: the results are identical for every number of handles.  Only the delivered lines' bytes
+    // come back.  The pattern must not contain 0x0A.
+    std::vector<Result> lines_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const std::string &pattern,
+                                             bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20)
+    {
+        if (pattern.empty() || pattern.size() > ZARC_GPU_SEARCH_MAX_PATTERN) throw Error(ZARC_GPU_E_PARAM, "the pattern has 1 to 256 bytes");
+        if (pattern.find('\n') != std::string::npos) throw Error(ZARC_GPU_E_PARAM, "the pattern must not contain a newline");
+        if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) throw Error(ZARC_GPU_E_PARAM, "max_line is 1 to 65536");
+        const Search s{&pattern, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, true, max_lines, max_line, rec_cap};
+        std::vector<Result> out = run_frames(archive, archive_len, wanted, false, &s);
+        size_t left = rec_cap;
+        for (Result &r : out) { // the delivery rule over the merged list (a handle saw fewer frames in front of this one: it delivered no less)
+            if (r.line_records.size() > left) r.line_records.resize(left);
+            left -= r.line_records.size();
+        }
+        return out;
+    }
+
   private:
-    struct Search { const std::string *pattern; unsigned flags; };
+    struct Search { const std::string *pattern; unsigned flags; bool lines = false; uint64_t max_lines = 0, max_line = 0; size_t rec_cap = 0; };
     std::vector<Result> run_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, bool with_data, const Search *search = nullptr)
     {
         const size_t n = wanted.size();
@@ -435,7 +461,26 @@ class FrameReader {
                 const Frame &f = wanted[idx[j]];
                 fp[j] = archive + f.offset; fl[j] = f.length; ul[j] = f.uncompressed; dp[j] = out[idx[j]].data.data(); expect[j] = f.digest;
             }
-            rc[d] = search    ? zarc_gpu_search_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
+            // lines: no frame holds more matching lines than it has room for matches, so a share's records never need more than this -- and
+            // neither does its text buffer, which the call wants rec_cap * max_line bytes large (never touched beyond what is delivered)
+            std::vector<uint64_t> nlines;
+            std::vector<zarc_gpu_line> rec;
+            std::unique_ptr<uint8_t, void (*)(void *)> text(nullptr, std::free);
+            size_t rec_cap = 0, rec_used = 0, text_used = 0;
+            if (search && search->lines) {
+                uint64_t room = 0;
+                for (size_t j = 0; j < m; j++) room += ul[j] / search->pattern->size() + 1;
+                rec_cap = (size_t)std::min<uint64_t>(search->rec_cap, room);
+                nlines.resize(m); rec.resize(rec_cap);
+                text.reset((uint8_t *)std::malloc(std::max<size_t>(1, rec_cap * (size_t)search->max_line)));
+                if (!text) { rc[d] = ZARC_GPU_E_NOMEM; return; }
+            }
+            rc[d] = search && search->lines
+                        ? zarc_gpu_search_lines_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
+                                                      search->pattern->data(), search->pattern->size(), search->flags, search->max_lines, search->max_line,
+                                                      (uint8_t(*)[32])got.data(), status.data(), count.data(), first.data(), nlines.data(), rec.data(), rec_cap,
+                                                      &rec_used, text.get(), rec_cap * (size_t)search->max_line, &text_used)
+                    : search  ? zarc_gpu_search_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
                                                       search->pattern->data(), search->pattern->size(), search->flags, (uint8_t(*)[32])got.data(),
                                                       status.data(), count.data(), first.data())
                     : with_data ? zarc_gpu_unpack_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), dp.data(), (const uint8_t(*)[32])expect.data(),
@@ -451,6 +496,11 @@ class FrameReader {
                 if (decoded) r.verify = got[j] == expect[j]; // a mismatch is reported, not fatal (zarc-cli/src/unpack.rs:118-120)
                 else r.data.clear();
                 if (search) { r.count = count[j]; if (first[j] != ZARC_GPU_SEARCH_NONE) r.first = first[j]; }
+                if (search && search->lines) r.lines = nlines[j];
+            }
+            for (size_t k = 0; k < rec_used; k++) {
+                const zarc_gpu_line &l = rec[k];
+                out[idx[l.frame]].line_records.push_back(Result::Line{l.start, l.length, l.number, l.match, std::vector<uint8_t>(text.get() + l.text_off, text.get() + l.text_off + l.text_len)});
             }
         };
         if (g == 1) unpack_share(0);
