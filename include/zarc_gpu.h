@@ -356,6 +356,56 @@ int zarc_gpu_search_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_fr
                                        int *status, uint64_t *count, uint64_t *first, uint64_t *lines, zarc_gpu_line *rec /* HOST array */,
                                        size_t rec_cap, size_t *rec_used, void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
 
+/* ---- search, a set: 1 .. ZARC_GPU_SEARCH_MAX_SET fixed strings in ONE pass ---------------------------------------------------------------- */
+/* What `grep -F -f list` answers: the frames are decoded, judged and hashed once and their content is read once, however many patterns the
+ * set holds.  A set is `count` patterns, pattern k = bytes[off[k] .. off[k] + len[k]), each of 1 .. ZARC_GPU_SEARCH_MAX_PATTERN bytes; all
+ * of it is HOST memory in every form.  Duplicates and patterns that are prefixes of one another are allowed.
+ *   - Pattern k MATCHES at p when content[p .. p + len[k]) == pattern k, with p + len[k] <= the frame's length: the frame-end rule is per
+ *     pattern (a short one may match where a longer one of the set is cut off).  ZARC_GPU_SEARCH_ICASE folds every pattern and the content
+ *     exactly as zarc_gpu_search_batch defines it.
+ *   - count[i] = the start positions at which AT LEAST ONE pattern matches (a position counts once, however many match there);
+ *     first[i] = the lowest of them, which[i] = the lowest k that matches at first[i]; both ZARC_GPU_SEARCH_NONE without a match.
+ *   - hits[k] (may be NULL; count words for the whole call, not per frame) = the sum over all searched frames of the call of the start
+ *     positions at which pattern k matches.
+ *   - status, digest, which frames are searched: as zarc_gpu_search_batch.  A frame that did not decode: count 0, first and which
+ *     ZARC_GPU_SEARCH_NONE, nothing added to hits.  A set of one pattern gives exactly zarc_gpu_search_batch's count and first.
+ *   - ZARC_GPU_E_PARAM: everything zarc_gpu_search_batch refuses; a NULL set or member of it; count 0 or above the maximum; a len of 0 or
+ *     above ZARC_GPU_SEARCH_MAX_PATTERN; a missing `which`.  n == 0: ZARC_GPU_OK -- the set is validated all the same and hits zeroed.
+ *   - The lines forms are zarc_gpu_search_lines_batch* word for word, with "a matching start position" being one of the union: a line with
+ *     matches of several patterns is one line, rec.match its lowest matching position.  No pattern may contain 0x0A (ZARC_GPU_E_PARAM).
+ *   - Results are the same for every ZARC_GPU_PX_SCRATCH_MB, every chunking, host and device form.  zarc_gpu_last_copy_bytes: as the
+ *     one-pattern calls (the compiled set is not content).  zarc_gpu_last_kernel_ms: ZARC_GPU_T_SEARCH covers the set's scan kernels,
+ *     ZARC_GPU_T_LINES the line kernels.
+ *   - Cost: the pass of zarc_gpu_search_batch with a table lookup per position in place of a compare; the worst case is that call's, times
+ *     the patterns that share a position's first bytes. */
+#define ZARC_GPU_SEARCH_MAX_SET 1024
+typedef struct {
+    const void *bytes;     /* the patterns' bytes */
+    const uint64_t *off;   /* count offsets into bytes */
+    const uint64_t *len;   /* count lengths, 1 .. ZARC_GPU_SEARCH_MAX_PATTERN */
+    size_t count;          /* 1 .. ZARC_GPU_SEARCH_MAX_SET */
+} zarc_gpu_pattern_set;    /* all HOST memory */
+int zarc_gpu_search_set_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                              const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const zarc_gpu_pattern_set *set, unsigned flags,
+                              uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *which,
+                              uint64_t *hits /* set->count words or NULL */);
+int zarc_gpu_search_set_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                     const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const zarc_gpu_pattern_set *set /* HOST */,
+                                     unsigned flags, uint8_t *digest /* n*32 */, int *status, uint64_t *count, uint64_t *first, uint64_t *which,
+                                     uint64_t *hits /* set->count words or NULL */);
+int zarc_gpu_search_set_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                    const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const zarc_gpu_pattern_set *set, unsigned flags,
+                                    uint64_t max_lines /* per frame; 0 = no limit */, uint64_t max_line /* 1..65536 */,
+                                    uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *which,
+                                    uint64_t *hits /* or NULL */, uint64_t *lines /* n */, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used,
+                                    void *text, size_t text_cap, size_t *text_used);
+int zarc_gpu_search_set_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                           const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const zarc_gpu_pattern_set *set /* HOST */,
+                                           unsigned flags, uint64_t max_lines, uint64_t max_line, uint8_t *digest /* n*32 */, int *status,
+                                           uint64_t *count, uint64_t *first, uint64_t *which, uint64_t *hits /* or NULL */, uint64_t *lines,
+                                           zarc_gpu_line *rec /* HOST array */, size_t rec_cap, size_t *rec_used, void *d_text /* DEVICE pointer */,
+                                           size_t text_cap, size_t *text_used);
+
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN]);
@@ -380,8 +430,8 @@ enum {
     ZARC_GPU_T_DEC_SEQS = 7,  /* decoder stage 2: sequence entropy decoding (zarc_zdec_seqs)             */
     ZARC_GPU_T_DEC_LITS = 8,  /* decoder stage 2: Huffman literals (zarc_zdec_literals, side stream)      */
     ZARC_GPU_T_DEC_FRAMES = 9,/* decoder frame pass (zarc_zstd_frames + the inline decoder for the rest)  */
-    ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan, summed over the parts of a call; < 0 or 0 after any other call */
-    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan (a set: zarc_set_scan and zarc_set_which), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set: its twins of mark and emit), summed over the parts of a call; < 0 or 0 after any other call */
     ZARC_GPU_T_COUNT = 12
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);

@@ -37,6 +37,7 @@ T_SEARCH = 10  # zarc_search_scan of a search call (summed over its parts)
 T_LINES = 11   # zarc_lines_* of a search_lines call (summed over its parts)
 # zarc_gpu_search_batch*: flags, the longest pattern, first[i] of a frame without a match
 SEARCH_ICASE, SEARCH_MAX_PATTERN, SEARCH_NONE = 1, 256, 2 ** 64 - 1
+SEARCH_MAX_SET = 1024  # zarc_gpu_search_set_*: the largest set
 LINES_MAX_LINE = 65536  # zarc_gpu_search_lines_batch*: the largest max_line
 
 EXPORTS = [
@@ -45,6 +46,7 @@ EXPORTS = [
     "zarc_gpu_pack_batch", "zarc_gpu_pack_batch_device", "zarc_gpu_pack_batch_dedup", "zarc_gpu_pack_batch_device_dedup", "zarc_gpu_unpack_batch", "zarc_gpu_unpack_batch_device",
     "zarc_gpu_verify_batch", "zarc_gpu_verify_batch_device", "zarc_gpu_last_copy_bytes", "zarc_gpu_repack_batch", "zarc_gpu_repack_batch_device",
     "zarc_gpu_search_batch", "zarc_gpu_search_batch_device", "zarc_gpu_search_lines_batch", "zarc_gpu_search_lines_batch_device",
+    "zarc_gpu_search_set_batch", "zarc_gpu_search_set_batch_device", "zarc_gpu_search_set_lines_batch", "zarc_gpu_search_set_lines_batch_device",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -62,6 +64,27 @@ class Params(ctypes.Structure):
 class Line(ctypes.Structure):
     """zarc_gpu_line: one matching line of a search_lines call"""
     _fields_ = [(n, ctypes.c_uint64) for n in ("frame", "start", "length", "number", "match", "text_off", "text_len")]
+
+
+class PatternSet(ctypes.Structure):
+    """zarc_gpu_pattern_set: the patterns of a search_set call (host memory)"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("off", ctypes.POINTER(ctypes.c_uint64)), ("len", ctypes.POINTER(ctypes.c_uint64)), ("count", ctypes.c_size_t)]
+
+    @classmethod
+    def of(cls, patterns):
+        """-> the structure over `patterns` (a list of bytes); it keeps what it points to alive"""
+        pats = [bytes(p) for p in patterns]
+        n = len(pats)
+        s = cls()
+        s._blob = ctypes.create_string_buffer(b"".join(pats), max(sum(len(p) for p in pats), 1))
+        s._off = (ctypes.c_uint64 * max(n, 1))()
+        s._len = (ctypes.c_uint64 * max(n, 1))()
+        at = 0
+        for k, p in enumerate(pats):
+            s._off[k], s._len[k] = at, len(p)
+            at += len(p)
+        s.bytes, s.off, s.len, s.count = ctypes.cast(s._blob, ctypes.c_void_p), s._off, s._len, n
+        return s
 
 
 class ZarcGpuError(RuntimeError):
@@ -118,6 +141,13 @@ def load(path=None):
     lib.zarc_gpu_search_lines_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vp, sz, c.c_uint, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, lp, sz, szp, vp, sz, szp]
     lib.zarc_gpu_search_lines_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, sz, c.c_uint, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, lp, sz,
                                                        szp, vp, sz, szp]
+    sp = c.POINTER(PatternSet)
+    lib.zarc_gpu_search_set_batch.argtypes = [vp, sz, vpp, szp, szp, vp, sp, c.c_uint, vp, ip, u64p, u64p, u64p, u64p]
+    lib.zarc_gpu_search_set_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, sp, c.c_uint, vp, ip, u64p, u64p, u64p, u64p]
+    lib.zarc_gpu_search_set_lines_batch.argtypes = [vp, sz, vpp, szp, szp, vp, sp, c.c_uint, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, u64p, u64p, lp, sz,
+                                                    szp, vp, sz, szp]
+    lib.zarc_gpu_search_set_lines_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, sp, c.c_uint, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, u64p, u64p,
+                                                           lp, sz, szp, vp, sz, szp]
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

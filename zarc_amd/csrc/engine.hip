@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <new>
 #include <numeric>
@@ -114,6 +115,9 @@ struct zarc_gpu {
     DevBuf d_rp_order, d_rp_xxh; // zarc_repack_plan: the caller's index of every frame of the decoder's order; XXH64 by entry for frame assembly
     // search (zarc_gpu_search_batch*): zarc_search_scan over d_vout behind the verdict of a verify pass
     DevBuf d_srch_pat, d_srch_slices, d_srch_count, d_srch_first; // the (folded) pattern; slice prefix, matches and lowest match of every frame (decoder order)
+    // a set of patterns (zarc_gpu_search_set_*): zarc_set_scan / zarc_set_which in place of zarc_search_scan
+    DevBuf d_set, d_set_hits, d_set_which;      // the compiled set (search_upload_set); hits of every pattern in this part; lowest matching pattern of every frame (decoder order)
+    ZarcSetDesc set_desc{};                     // where things lie in d_set
     // the matching lines of a search (zarc_gpu_search_lines_batch*): zarc_lines_* behind zarc_search_scan, per part
     DevBuf d_ln_slices, d_ln_lines;             // ZarcLineSlice of every slice; matching lines of every frame (decoder order)
     DevBuf d_ln_base, d_ln_deliver;             // what the host decided: first record and number of records of every frame (decoder order)
@@ -647,6 +651,10 @@ struct SearchReq {
     uint32_t m, icase;
     uint64_t *count, *first;   // host, in the caller's order: matching start positions; the lowest, or ZARC_GPU_SEARCH_NONE
     const LinesReq *ln = nullptr;
+    // a set of patterns in place of the one (zarc_gpu_search_set_*): d_pattern and m are not looked at
+    const ZarcSetDesc *set = nullptr; // the handle's, made by search_upload_set; the blob is h->d_set
+    uint64_t *which = nullptr; // host, in the caller's order: the lowest pattern that matches at first[i], or ZARC_GPU_SEARCH_NONE
+    uint64_t *hits = nullptr;  // host, per pattern, or null: every part ADDS the positions at which the pattern matches in its frames
 };
 int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
 static_assert(sizeof(ZarcLineRec) == sizeof(zarc_gpu_line), "the device's record is the caller's");
@@ -1521,6 +1529,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     ZHIP(hipGetLastError());
     int e5 = -1, e6 = -1, e7 = -1;
     uint64_t slices_total = 0;
+    size_t set_lds = 0; // a set search: bytes of the set's image in LDS
     float lines_ms2 = 0;
     if (srch) { // ---- search: the decoded bytes are judged; look through those of the frames that decoded, where they lie
         std::vector<uint64_t> slices(n + 1, 0);
@@ -1532,15 +1541,34 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         ZHIP(h->d_srch_first.reserve(n * 4));
         ZHIP(hipMemsetAsync(h->d_srch_count.p, 0, n * 4, h->stream));
         ZHIP(hipMemsetAsync(h->d_srch_first.p, 0xFF, n * 4, h->stream));
+        if (srch->set) {
+            set_lds = (size_t)srch->set->lds_words * 4;
+            ZHIP(h->d_set_which.reserve(n * 4));
+            if (srch->hits) ZHIP(hipMemsetAsync(h->d_set_hits.p, 0, (size_t)srch->set->count * 4, h->stream)); // (reserved by search_upload_set)
+        }
         ZHIP(t.mark(&e5));
-        hipLaunchKernelGGL(zarc_search_scan, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                           b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_pattern, srch->m, srch->icase,
-                           h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>());
+        if (srch->set) {
+            hipLaunchKernelGGL(zarc_set_scan, dim3((unsigned)slices[n]), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase,
+                               h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>(), srch->hits ? h->d_set_hits.as<uint32_t>() : (uint32_t *)nullptr);
+            hipLaunchKernelGGL(zarc_set_which, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (uint32_t)n, (const uint8_t *)d_dst_base, b_dst_off.as<uint64_t>(),
+                               h->d_raw_len.as<uint64_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase, h->d_srch_count.as<uint32_t>(),
+                               h->d_srch_first.as<uint32_t>(), h->d_set_which.as<uint32_t>());
+        } else {
+            hipLaunchKernelGGL(zarc_search_scan, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_pattern, srch->m, srch->icase,
+                               h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>());
+        }
         ZHIP(hipGetLastError());
         ZHIP(t.mark(&e6));
         if (srch->ln) { // ---- lines, first half: what every slice holds, what every slice must know of its neighbours, lines[] of every frame
             ZHIP(h->d_ln_slices.reserve(slices[n] * sizeof(ZarcLineSlice)));
             ZHIP(h->d_ln_lines.reserve(n * 4));
+            if (srch->set)
+                hipLaunchKernelGGL(zarc_lines_mark_set, dim3((unsigned)slices[n]), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                                   b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase,
+                                   h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
+            else
             hipLaunchKernelGGL(zarc_lines_mark, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
                                b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_pattern, srch->m, srch->icase,
                                h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
@@ -1564,11 +1592,21 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         ZHIP(hipMemcpyAsync(sc.data(), h->d_srch_count.p, n * 4, hipMemcpyDeviceToHost, h->stream));
         ZHIP(hipMemcpyAsync(sf.data(), h->d_srch_first.p, n * 4, hipMemcpyDeviceToHost, h->stream));
     }
+    std::vector<uint32_t> sw, sh;
+    if (srch && srch->set) {
+        sw.resize(n);
+        ZHIP(hipMemcpyAsync(sw.data(), h->d_set_which.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (srch->hits) { sh.resize(srch->set->count); ZHIP(hipMemcpyAsync(sh.data(), h->d_set_hits.p, sh.size() * 4, hipMemcpyDeviceToHost, h->stream)); }
+    }
     std::vector<uint32_t> ln_lines;
     if (srch && srch->ln) { ln_lines.resize(n); ZHIP(hipMemcpyAsync(ln_lines.data(), h->d_ln_lines.p, n * 4, hipMemcpyDeviceToHost, h->stream)); }
     ZHIP(hipStreamSynchronize(h->stream));
     for (size_t i = 0; i < n; i++) { status[order[i]] = st[i]; memcpy(digest + (size_t)order[i] * 32, dg + i * 32, 32); }
     if (srch) for (size_t i = 0; i < n; i++) { srch->count[order[i]] = sc[i]; srch->first[order[i]] = sf[i] == 0xFFFFFFFFu ? ZARC_GPU_SEARCH_NONE : sf[i]; }
+    if (srch && srch->set) {
+        for (size_t i = 0; i < n; i++) srch->which[order[i]] = sw[i] == 0xFFFFFFFFu ? ZARC_GPU_SEARCH_NONE : sw[i];
+        for (size_t k = 0; k < sh.size(); k++) srch->hits[k] += sh[k]; // (32-bit per part, 64-bit over the call)
+    }
     if (srch && srch->ln) { // ---- lines, second half: the delivery rule in the caller's order, then records and text of what this part delivers
         const LinesReq &ln = *srch->ln;
         LinesRun &run = *ln.run;
@@ -1594,6 +1632,11 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
             ZHIP(hipMemsetAsync(h->d_ln_rec.p, 0, nrec * sizeof(ZarcLineRec), h->stream)); // (a record nobody wrote would name no frame and no text)
             int e8, e9;
             ZHIP(t.mark(&e8));
+            if (srch->set)
+                hipLaunchKernelGGL(zarc_lines_emit_set, dim3((unsigned)slices_total), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                                   b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase, h->d_ln_slices.as<ZarcLineSlice>(),
+                                   h->d_ln_base.as<uint64_t>(), h->d_ln_deliver.as<uint32_t>(), ln.max_line, h->d_ln_rec.as<ZarcLineRec>());
+            else
             hipLaunchKernelGGL(zarc_lines_emit, dim3((unsigned)slices_total), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
                                b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), srch->d_pattern, srch->m, srch->icase, h->d_ln_slices.as<ZarcLineSlice>(),
                                h->d_ln_base.as<uint64_t>(), h->d_ln_deliver.as<uint32_t>(), ln.max_line, h->d_ln_rec.as<ZarcLineRec>());
@@ -1707,7 +1750,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
         if (chk) { sub = *chk; sub.first_bad += a; if (chk->entry_map) sub.entry_map += a; else sub.entry0 += (uint32_t)a; }
         SearchReq ssub{};
         LinesReq lsub{};
-        if (srch) { ssub = *srch; ssub.count += a; ssub.first += a; }
+        if (srch) { ssub = *srch; ssub.count += a; ssub.first += a; if (srch->which) ssub.which += a; }
         if (srch && srch->ln) { lsub = *srch->ln; lsub.lines += a; lsub.frame0 += a; ssub.ln = &lsub; }
         rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
                                  digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr);
@@ -1798,12 +1841,14 @@ int lines_check_args(zarc_gpu_t *h, const void *pattern, size_t pattern_len, uin
 }
 // one part of a lines call (the whole of the device form, a chunk of the host form): search's pass with the line kernels behind it
 int search_lines_part(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, const uint64_t *raw_len,
-                      const uint8_t *expect, size_t pattern_len, unsigned flags, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, const LinesReq &ln)
+                      const uint8_t *expect, size_t pattern_len, unsigned flags, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, const LinesReq &ln,
+                      uint64_t *which = nullptr, uint64_t *hits = nullptr) // which: the handle's set (search_upload_set) in place of its pattern
 {
     int rc = check_common(h, n);
     if (rc) return rc;
     SearchReq srch{h->d_srch_pat.as<uint8_t>(), (uint32_t)pattern_len, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
     srch.ln = &ln;
+    if (which) { srch.set = &h->set_desc; srch.which = which; srch.hits = hits; }
     return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
 }
 } // namespace
@@ -1828,6 +1873,130 @@ int zarc_gpu_search_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_fr
     LinesRun run;
     const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, (uint8_t *)d_text, nullptr, &run};
     rc = search_lines_part(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, pattern_len, flags, digest, status, count, first, ln);
+    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
+    return rc;
+}
+
+} // extern "C"
+namespace {
+// what every set entry point checks the same way, before anything else is looked at (search_check_args for a set); lines: no 0x0A either
+int search_set_check_args(zarc_gpu_t *h, const zarc_gpu_pattern_set *set, unsigned flags, bool lines, const void *digest, const int *status, const uint64_t *count,
+                          const uint64_t *first, const uint64_t *which)
+{
+    if (!h) return ZARC_GPU_E_PARAM;
+    if (!set || !set->bytes || !set->off || !set->len) { set_error(h, "search_set: a set and its members are needed"); return ZARC_GPU_E_PARAM; }
+    if (set->count == 0 || set->count > ZARC_GPU_SEARCH_MAX_SET) { set_error(h, "search_set: a set has 1 to 1024 patterns"); return ZARC_GPU_E_PARAM; }
+    for (size_t k = 0; k < set->count; k++) {
+        if (set->len[k] == 0 || set->len[k] > ZARC_GPU_SEARCH_MAX_PATTERN) { set_error(h, "search_set: a pattern has 1 to 256 bytes"); return ZARC_GPU_E_PARAM; }
+        if (lines && memchr((const uint8_t *)set->bytes + set->off[k], 0x0A, set->len[k])) { set_error(h, "search_set_lines: a pattern must not contain a newline"); return ZARC_GPU_E_PARAM; }
+    }
+    if (flags & ~(unsigned)ZARC_GPU_SEARCH_ICASE) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
+    if (!digest || !status || !count || !first || !which) return ZARC_GPU_E_PARAM;
+    return 0;
+}
+uint32_t ceil_log2(uint32_t v) { uint32_t l = 0; while ((1u << l) < v) l++; return l; }
+// The set goes up once per call, compiled into what zdec_search_set.hip reads (the layout is described there and at ZarcSetDesc) and folded
+// here when the text is folded there.  Filters and tables are sized from the number of distinct keys of each length class.
+int search_upload_set(zarc_gpu_t *h, const zarc_gpu_pattern_set *set, unsigned flags)
+{
+    const uint32_t K = (uint32_t)set->count;
+    const bool fold = (flags & ZARC_GPU_SEARCH_ICASE) != 0;
+    std::map<uint32_t, std::vector<uint32_t>> keys[4]; // per class: the patterns that share a key, ascending
+    std::vector<uint32_t> pat(2 * (size_t)K), bytes;
+    ZarcSetDesc sd{};
+    sd.count = K; sd.min_len = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < K; k++) {
+        const uint8_t *src = (const uint8_t *)set->bytes + set->off[k];
+        const uint32_t len = (uint32_t)set->len[k], w0 = (uint32_t)bytes.size();
+        bytes.resize(w0 + (len + 3) / 4, 0);
+        for (uint32_t b = 0; b < len; b++) {
+            uint8_t v = src[b];
+            if (fold && v >= 'A' && v <= 'Z') v |= 0x20;
+            bytes[w0 + b / 4] |= (uint32_t)v << (8 * (b & 3));
+        }
+        pat[2 * k] = w0; pat[2 * k + 1] = len;
+        const uint32_t c = std::min(len, 4u) - 1; // (the word's unused bytes are 0: the word of a short pattern is its key)
+        keys[c][bytes[w0]].push_back(k);
+        sd.min_len = std::min(sd.min_len, len);
+    }
+    uint32_t cur = 0;
+    for (uint32_t c = 0; c < 4; c++) {
+        if (keys[c].empty()) continue;
+        const uint32_t nk = (uint32_t)keys[c].size();
+        sd.classes |= 1u << c;
+        sd.flog[c] = c == 0 ? 8 : std::max(6u, ceil_log2(16 * nk));
+        sd.tlog[c] = std::max(1u, ceil_log2(2 * nk));
+        sd.foff[c] = cur; cur += (1u << sd.flog[c]) / 32;
+        sd.toff[c] = cur; cur += 2u << sd.tlog[c];
+    }
+    sd.lds_words = cur;
+    if ((size_t)cur * 4 > 40960) { set_error(h, "search_set: the compiled set is too large"); return ZARC_GPU_E_PARAM; } // (cannot happen with 1024 patterns: 9 words per key at the most)
+    std::vector<uint32_t> blob(cur, 0);
+    for (uint32_t c = 0; c < 4; c++)
+        for (const auto &kv : keys[c]) {
+            const uint32_t key = kv.first, hash = key * ZARC_SET_HASH;
+            const uint32_t bit = c == 0 ? key : hash >> (32 - sd.flog[c]);
+            blob[sd.foff[c] + bit / 32] |= 1u << (bit & 31);
+            uint32_t slot = hash >> (32 - sd.tlog[c]);
+            while (blob[sd.toff[c] + 2 * slot + 1]) slot = (slot + 1) & ((1u << sd.tlog[c]) - 1);
+            blob[sd.toff[c] + 2 * slot] = key;
+            blob[sd.toff[c] + 2 * slot + 1] = (uint32_t)blob.size(); // (never 0: the image lies in front)
+            blob.push_back((uint32_t)kv.second.size());
+            blob.insert(blob.end(), kv.second.begin(), kv.second.end());
+        }
+    sd.pat_off = (uint32_t)blob.size();
+    const uint32_t bytes_off = sd.pat_off + 2 * K;
+    for (uint32_t k = 0; k < K; k++) { blob.push_back(bytes_off + pat[2 * k]); blob.push_back(pat[2 * k + 1]); }
+    blob.insert(blob.end(), bytes.begin(), bytes.end());
+    ZHIP(h->d_set.reserve(blob.size() * 4));
+    ZHIP(h->d_set_hits.reserve((size_t)K * 4));
+    ZHIP(hipMemcpy(h->d_set.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+    h->set_desc = sd;
+    return 0;
+}
+} // namespace
+extern "C" {
+
+// zarc_gpu_search_batch_device with zarc_set_scan and zarc_set_which in place of zarc_search_scan
+int zarc_gpu_search_set_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                     const uint64_t *raw_len, const uint8_t *expect, const zarc_gpu_pattern_set *set, unsigned flags,
+                                     uint8_t *digest, int *status, uint64_t *count, uint64_t *first, uint64_t *which, uint64_t *hits)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if ((rc = search_set_check_args(h, set, flags, false, digest, status, count, first, which))) return rc;
+    if (hits && !h->nested) memset(hits, 0, set->count * sizeof *hits); // (the host form has done it for all its chunks)
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
+    for (size_t i = 0; i < n; i++)
+        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
+    if (!h->nested && (rc = search_upload_set(h, set, flags))) return rc;
+    SearchReq srch{nullptr, 0, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
+    srch.set = &h->set_desc; srch.which = which; srch.hits = hits;
+    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
+}
+
+// zarc_gpu_search_lines_batch_device with the set's kernels in place of the pattern's
+int zarc_gpu_search_set_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                           const uint64_t *raw_len, const uint8_t *expect, const zarc_gpu_pattern_set *set, unsigned flags,
+                                           uint64_t max_lines, uint64_t max_line, uint8_t *digest, int *status, uint64_t *count, uint64_t *first,
+                                           uint64_t *which, uint64_t *hits, uint64_t *lines, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used,
+                                           void *d_text, size_t text_cap, size_t *text_used)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if ((rc = search_set_check_args(h, set, flags, true, digest, status, count, first, which))) return rc;
+    if ((rc = lines_check_args(h, "", 0, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used))) return rc;
+    *rec_used = 0; *text_used = 0;
+    if (hits) memset(hits, 0, set->count * sizeof *hits);
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
+    for (size_t i = 0; i < n; i++)
+        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
+    if ((rc = search_upload_set(h, set, flags))) return rc;
+    LinesRun run;
+    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, (uint8_t *)d_text, nullptr, &run};
+    rc = search_lines_part(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, 0, flags, digest, status, count, first, ln, which, hits);
     *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
     return rc;
 }
@@ -2362,12 +2531,14 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 // The chunk loop of zarc_gpu_unpack_batch without its outbound half: chunk c+1's frames come in while chunk c is decoded and judged;
 // nothing but statuses and digests goes back.  A chunk's decoded bytes live in the handle's scratch (unpack_device_split), so the
 // chunks are cut by the same weight as unpack's.
-// With a pattern (zarc_gpu_search_batch) every chunk is searched as well, and two more words per frame go back.
+// With a pattern (zarc_gpu_search_batch) every chunk is searched as well, and two more words per frame go back; with a set of them
+// (zarc_gpu_search_set_batch) three, and every chunk adds to the call's hits.
 } // extern "C"
 namespace {
 int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                      const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const void *pattern,
-                     size_t pattern_len, unsigned flags, uint64_t *count, uint64_t *first, const LinesReq *ln = nullptr)
+                     size_t pattern_len, unsigned flags, uint64_t *count, uint64_t *first, const LinesReq *ln = nullptr,
+                     const zarc_gpu_pattern_set *set = nullptr, uint64_t *which = nullptr, uint64_t *hits = nullptr)
 {
     int rc = 0;
     if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
@@ -2415,8 +2586,12 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
             LinesReq sub = *ln;
             sub.lines += i0; sub.frame0 += i0;
             rc = search_lines_part(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0, expect ? (const uint8_t *)expect[i0] : nullptr,
-                                   pattern_len, flags, (uint8_t *)digest[i0], status + i0, count + i0, first + i0, sub);
-        } else if (pattern)
+                                   pattern_len, flags, (uint8_t *)digest[i0], status + i0, count + i0, first + i0, sub, set ? which + i0 : nullptr, hits);
+        } else if (set)
+            rc = zarc_gpu_search_set_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
+                                                  expect ? (const uint8_t *)expect[i0] : nullptr, set, flags, (uint8_t *)digest[i0], status + i0,
+                                                  count + i0, first + i0, which + i0, hits);
+        else if (pattern)
             rc = zarc_gpu_search_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
                                               expect ? (const uint8_t *)expect[i0] : nullptr, pattern, pattern_len, flags, (uint8_t *)digest[i0], status + i0,
                                               count + i0, first + i0);
@@ -2471,6 +2646,41 @@ int zarc_gpu_search_lines_batch(zarc_gpu_t *h, size_t n, const void *const *fram
     LinesRun run;
     const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, nullptr, (uint8_t *)text, &run};
     rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, pattern, pattern_len, flags, count, first, &ln);
+    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
+    return rc;
+}
+
+// zarc_gpu_search_batch's chunk loop with the set's kernels behind every chunk's verdict: 60 bytes per frame come back, and the hits
+int zarc_gpu_search_set_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                              const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const zarc_gpu_pattern_set *set, unsigned flags,
+                              uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *which, uint64_t *hits)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if ((rc = search_set_check_args(h, set, flags, false, digest, status, count, first, which))) return rc;
+    if (hits) memset(hits, 0, set->count * sizeof *hits);
+    if (n == 0) return ZARC_GPU_OK;
+    if ((rc = search_upload_set(h, set, flags))) return rc;
+    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, 0, flags, count, first, nullptr, set, which, hits);
+}
+// ... and with the line kernels behind every chunk's search
+int zarc_gpu_search_set_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                    const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const zarc_gpu_pattern_set *set, unsigned flags, uint64_t max_lines,
+                                    uint64_t max_line, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first,
+                                    uint64_t *which, uint64_t *hits, uint64_t *lines, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *text,
+                                    size_t text_cap, size_t *text_used)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if ((rc = search_set_check_args(h, set, flags, true, digest, status, count, first, which))) return rc;
+    if ((rc = lines_check_args(h, "", 0, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used))) return rc;
+    *rec_used = 0; *text_used = 0;
+    if (hits) memset(hits, 0, set->count * sizeof *hits);
+    if (n == 0) return ZARC_GPU_OK;
+    if ((rc = search_upload_set(h, set, flags))) return rc;
+    LinesRun run;
+    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, nullptr, (uint8_t *)text, &run};
+    rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, 0, flags, count, first, &ln, set, which, hits);
     *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
     return rc;
 }

@@ -224,6 +224,28 @@ __global__ void zarc_lines_emit(uint32_t n, const uint64_t *slice_prefix, const 
                                 const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
 __global__ void zarc_lines_scan(uint64_t nrec, ZarcLineRec *rec, uint64_t *total);
 __global__ void zarc_lines_gather(uint64_t nrec, const ZarcLineRec *rec, const uint8_t *dec_base, const uint64_t *dec_off, uint8_t *text);
+// a set of patterns in one pass (zdec_search_set.hip).  `set` is the blob search_upload_set (engine.hip) compiles: words [0, lds_words) are
+// the image a workgroup keeps in LDS -- per length class c (0, 1, 2: patterns of 1, 2, 3 bytes; 3: of 4 bytes and more, keyed by their
+// first four) a bit filter of 1 << flog[c] bits at word foff[c] and an exact table of 1 << tlog[c] slots {key, list} at word toff[c]
+// (list: a word index into the blob, 0 = an empty slot) -- then the lists {n, n pattern indices}, at word pat_off {first word of the
+// bytes, length} per pattern, and the patterns' bytes padded to words.  hits[k] += positions at which pattern k matches (may be null).
+constexpr uint32_t ZARC_SEARCH_MAX_SET = 1024;
+constexpr uint32_t ZARC_SET_HASH = 0x9E3779B1u; // filter bit and first table slot of a key: the top bits of key * this (one-byte class: the filter bit is the key)
+struct ZarcSetDesc {
+    uint32_t count, classes;      // patterns; bit c = the set holds patterns of class c
+    uint32_t lds_words, min_len;  // words of the LDS image; the shortest pattern
+    uint32_t pat_off;
+    uint32_t flog[4], tlog[4], foff[4], toff[4];
+};
+__global__ void zarc_set_scan(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                              const int32_t *status, ZarcSetDesc sd, const uint32_t *set, uint32_t icase, uint32_t *count, uint32_t *first, uint32_t *hits);
+__global__ void zarc_set_which(uint32_t n, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len, ZarcSetDesc sd, const uint32_t *set,
+                               uint32_t icase, const uint32_t *count, const uint32_t *first, uint32_t *which);
+__global__ void zarc_lines_mark_set(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                    const int32_t *status, ZarcSetDesc sd, const uint32_t *set, uint32_t icase, ZarcLineSlice *slices, uint32_t *lines);
+__global__ void zarc_lines_emit_set(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                    ZarcSetDesc sd, const uint32_t *set, uint32_t icase, const ZarcLineSlice *slices, const uint64_t *rec_base,
+                                    const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

@@ -225,6 +225,70 @@ class Engine:
             self.free(d_text)
         return self._lines_result(n, status, dig, count, first, lines, rec, rec_used.value, text)
 
+    def search_set_device(self, d_frames, frame_off, frame_len, raw_len, patterns, icase=False, expect=None):
+        """search_device for a set of patterns in one pass -> (results, hits) as search_set() gives them."""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        count, first, which = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        ps = _lib.PatternSet.of(patterns)
+        hits = (ctypes.c_uint64 * max(ps.count, 1))()
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        self._check(self.lib.zarc_gpu_search_set_batch_device(
+            self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            ctypes.byref(ps), _lib.SEARCH_ICASE if icase else 0, dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+            count.ctypes.data_as(u64p), first.ctypes.data_as(u64p), which.ctypes.data_as(u64p), hits))
+        return self._set_result(n, status, dig, count, first, which), [int(v) for v in hits[:ps.count]]
+
+    def search_set_lines_device(self, d_frames, frame_off, frame_len, raw_len, patterns, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+        """search_lines_device for a set of patterns -> (results, records, hits) as search_set_lines() gives them."""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        count, first, which, lines = (np.zeros(n, dtype=np.uint64) for _ in range(4))
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        ps = _lib.PatternSet.of(patterns)
+        hits = (ctypes.c_uint64 * max(ps.count, 1))()
+        rec = (_lib.Line * max(rec_cap, 1))()
+        rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
+        text_cap = rec_cap * max_line
+        d_text = self.malloc(max(text_cap, 1))
+        try:
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            self._check(self.lib.zarc_gpu_search_set_lines_batch_device(
+                self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+                ctypes.byref(ps), _lib.SEARCH_ICASE if icase else 0, max_lines, max_line,
+                dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), count.ctypes.data_as(u64p), first.ctypes.data_as(u64p),
+                which.ctypes.data_as(u64p), hits, lines.ctypes.data_as(u64p), rec, rec_cap, ctypes.byref(rec_used), ctypes.c_void_p(d_text), text_cap,
+                ctypes.byref(text_used)))
+            text = bytes(self.d2h(d_text, text_used.value)) if text_used.value else b""
+        finally:
+            self.free(d_text)
+        return self._set_lines_result(n, status, dig, count, first, which, lines, rec, rec_used.value, text) + ([int(v) for v in hits[:ps.count]],)
+
+    @staticmethod
+    def _set_result(n, status, dig, count, first, which):
+        none = lambda v: None if int(v) == _lib.SEARCH_NONE else int(v)
+        return [(int(status[i]), bytes(dig[i]), int(count[i]), none(first[i]), none(which[i])) for i in range(n)]
+
+    @staticmethod
+    def _set_lines_result(n, status, dig, count, first, which, lines, rec, rec_used, text):
+        none = lambda v: None if int(v) == _lib.SEARCH_NONE else int(v)
+        results = [(int(status[i]), bytes(dig[i]), int(count[i]), none(first[i]), none(which[i]), int(lines[i])) for i in range(n)]
+        records = [(r.frame, r.start, r.length, r.number, r.match, text[r.text_off:r.text_off + r.text_len]) for r in rec[:rec_used]]
+        return results, records
+
     @staticmethod
     def _lines_result(n, status, dig, count, first, lines, rec, rec_used, text):
         results = [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i]), int(lines[i])) for i in range(n)]
@@ -393,6 +457,57 @@ class Engine:
             dig.ctypes.data_as(ctypes.c_void_p), status, count, first, lines, rec, rec_cap, ctypes.byref(rec_used),
             text.ctypes.data_as(ctypes.c_void_p), text_cap, ctypes.byref(text_used)))
         return self._lines_result(n, status, dig, count, first, lines, rec, rec_used.value, bytes(text[:text_used.value]))
+
+    def search_set(self, frames, raw_lens, patterns, icase=False, expect=None):
+        """search() for a set of 1..1024 fixed byte strings in ONE pass -> (results, hits).  results[i] = (status, digest, count, first,
+        which): count = the start positions at which at least one pattern matches (a position counts once), first the lowest of them,
+        which the lowest index of a pattern matching there (both None without a match).  hits[k] = the positions at which pattern k
+        matches, summed over the frames of the call.  The frame-end rule is per pattern."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        count, first, which = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        ps = _lib.PatternSet.of(patterns)
+        hits = (ctypes.c_uint64 * max(ps.count, 1))()
+        self._check(self.lib.zarc_gpu_search_set_batch(self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+                                                       ctypes.byref(ps), _lib.SEARCH_ICASE if icase else 0, dig.ctypes.data_as(ctypes.c_void_p), status,
+                                                       count, first, which, hits))
+        return self._set_result(n, status, dig, count, first, which), [int(v) for v in hits[:ps.count]]
+
+    def search_set_lines(self, frames, raw_lens, patterns, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+        """search_lines() for a set of patterns -> (results, records, hits).  results[i] = (status, digest, count, first, which, lines) with
+        search_set()'s meaning; a line matches when a matching start position of ANY pattern lies in it, and a record's match is the lowest
+        such position of its line.  No pattern may contain 0x0A.  records and the caps are search_lines()'s."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        count, first, which, lines = ((ctypes.c_uint64 * n)() for _ in range(4))
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        ps = _lib.PatternSet.of(patterns)
+        hits = (ctypes.c_uint64 * max(ps.count, 1))()
+        rec = (_lib.Line * max(rec_cap, 1))()
+        rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
+        text_cap = rec_cap * max_line
+        text = np.empty(max(text_cap, 1), dtype=np.uint8)
+        self._check(self.lib.zarc_gpu_search_set_lines_batch(
+            self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            ctypes.byref(ps), _lib.SEARCH_ICASE if icase else 0, max_lines, max_line,
+            dig.ctypes.data_as(ctypes.c_void_p), status, count, first, which, hits, lines, rec, rec_cap, ctypes.byref(rec_used),
+            text.ctypes.data_as(ctypes.c_void_p), text_cap, ctypes.byref(text_used)))
+        return self._set_lines_result(n, status, dig, count, first, which, lines, rec, rec_used.value, bytes(text[:text_used.value])) + ([int(v) for v in hits[:ps.count]],)
 
     def repack(self, frames, raw_lens, expect=None):
         """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with

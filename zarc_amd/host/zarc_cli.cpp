@@ -197,6 +197,7 @@ int usage()
                          "         exit status 1 and nothing is left at PATH\n"
                          "       zarc grep [-i] [-l] [-b] [--hex] [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
                          "                 [--lines] [-n] [-c] [-a] [-m NUM] [--max-line BYTES] [--batch-lines N] PATTERN ARCHIVE\n"
+                         "       zarc grep ... (-e PATTERN | -f FILE)... [--tally] ARCHIVE\n"
                          "         searches the content of the files for PATTERN on the device, each distinct frame once, and writes nothing.  PATTERN is a\n"
                          "         fixed string of 1 to 256 bytes (grep -F), never a regular expression; --hex reads it as hex digits.  One line per file with\n"
                          "         a match: PATH:COUNT (overlapping occurrences count); -b adds :OFFSET of the first one, -l prints PATH alone, -i folds ASCII\n"
@@ -207,6 +208,12 @@ int usage()
                          "         `Binary file PATH matches` unless -a is given.  A line prints its first --max-line bytes (default 4096, 1 to 65536).\n"
                          "         --batch-lines N (default 1048576) is the number of lines one device call can bring back; what did not fit is searched again.\n"
                          "         PATTERN must not contain a newline in lines mode\n"
+                         "         -e PATTERN (any number of times) and -f FILE (one pattern per line; a CR stays part of it, an empty line is an error) give a\n"
+                         "         SET of up to 1024 patterns that is searched in one pass; ARCHIVE is then the only other argument and --hex applies to every\n"
+                         "         pattern.  Patterns that are equal (after -i) are searched once.  A position at which several patterns match counts once, a\n"
+                         "         line with matches of several is one line; the output is the same as for one PATTERN.  --tally prints, instead of the lines per\n"
+                         "         file, one line COUNT<TAB>PATTERN per pattern in the order given (as typed; zeros included): the positions at which it matches,\n"
+                         "         over the distinct frames searched\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -735,8 +742,8 @@ int cmd_verify(const std::vector<std::string> &a)
 }
 
 // `zarc grep`: which files contain this byte string?  Every distinct content frame behind the files that pass the filters is decoded,
-// judged and searched on the device (zarc_gpu_search_batch): the compressed bytes go up, a few words per frame come back, and a frame
-// that many files share is searched once.  Nothing is created, opened or changed in the file system.  Exit status: grep's.
+// judged and searched on the device (zarc_gpu_search_batch; with -e / -f / --tally a set of strings in one pass, zarc_gpu_search_set_batch):
+// the compressed bytes go up, a few words per frame come back, and a frame that many files share is searched once.  Nothing is created, opened or changed in the file system.  Exit status: grep's.
 int cmd_grep(const std::vector<std::string> &a)
 {
     std::string pattern, input, verify;
@@ -745,8 +752,25 @@ int cmd_grep(const std::vector<std::string> &a)
     bool lines_mode = false, numbers = false, count_lines = false, as_text = false; // lines mode (any of its flags selects it)
     long long max_per_file = 0, max_line = 4096, batch_lines = 1048576;
     int gpus = 1;
+    std::vector<std::string> typed; // -e / -f: the patterns of a set, as given
+    bool use_set = false, tally = false;
     for (size_t i = 0; i < a.size(); i++) {
         if (options && a[i] == "--filter" && i + 1 < a.size()) filters.emplace_back(a[++i]);
+        else if (options && a[i] == "-e" && i + 1 < a.size()) { typed.push_back(a[++i]); use_set = true; }
+        else if (options && a[i] == "-f" && i + 1 < a.size()) {
+            use_set = true;
+            std::ifstream in(a[++i], std::ios::binary);
+            if (!in) { std::fprintf(stderr, "Error: cannot read the pattern file %s\n", a[i].c_str()); return 2; }
+            const std::string all((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            for (size_t at = 0; at < all.size();) { // LF-terminated lines; a final LF opens no further line
+                const size_t nl = all.find('\n', at);
+                const std::string line = all.substr(at, nl == std::string::npos ? std::string::npos : nl - at);
+                if (line.empty()) { std::fprintf(stderr, "Error: an empty line in the pattern file %s\n", a[i].c_str()); return 2; }
+                typed.push_back(line);
+                at = nl == std::string::npos ? all.size() : nl + 1;
+            }
+        }
+        else if (options && a[i] == "--tally") tally = true;
         else if (options && a[i] == "--lines") lines_mode = true;
         else if (options && a[i] == "-m" && i + 1 < a.size()) { max_per_file = std::atoll(a[++i].c_str()); lines_mode = true; if (max_per_file < 1) return usage(); }
         else if (options && a[i] == "--max-line" && i + 1 < a.size()) { max_line = std::atoll(a[++i].c_str()); lines_mode = true; if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) return usage(); }
@@ -771,18 +795,44 @@ int cmd_grep(const std::vector<std::string> &a)
         else if (input.empty()) input = a[i];
         else return usage();
     }
+    if (use_set || tally) { // the set's patterns came with -e / -f (--tally alone: the one PATTERN is a set of one): ARCHIVE is the only other argument
+        if (use_set) { if (!have_pattern || !input.empty()) return usage(); input = pattern; }
+        else { if (!have_pattern) return usage(); typed.push_back(pattern); use_set = true; }
+        have_pattern = true;
+        if (typed.empty()) { std::fprintf(stderr, "Error: no pattern\n"); return 2; }
+    } else typed.push_back(pattern);
     if (!have_pattern || input.empty() || gpus < 1 || gpus > 64) return usage();
-    if (hex) {
-        std::string raw;
-        if (pattern.size() % 2) { std::fprintf(stderr, "Error: --hex wants an even number of hex digits\n"); return 2; }
-        for (size_t k = 0; k < pattern.size(); k += 2) {
-            if (!std::isxdigit((unsigned char)pattern[k]) || !std::isxdigit((unsigned char)pattern[k + 1])) { std::fprintf(stderr, "Error: --hex wants hex digits\n"); return 2; }
-            raw.push_back((char)std::stoi(pattern.substr(k, 2), nullptr, 16));
+    std::vector<std::string> given = typed; // the patterns' bytes
+    if (hex)
+        for (std::string &g : given) {
+            std::string raw;
+            if (g.size() % 2) { std::fprintf(stderr, "Error: --hex wants an even number of hex digits\n"); return 2; }
+            for (size_t k = 0; k < g.size(); k += 2) {
+                if (!std::isxdigit((unsigned char)g[k]) || !std::isxdigit((unsigned char)g[k + 1])) { std::fprintf(stderr, "Error: --hex wants hex digits\n"); return 2; }
+                raw.push_back((char)std::stoi(g.substr(k, 2), nullptr, 16));
+            }
+            g = raw;
         }
-        pattern = raw;
+    for (const std::string &g : given) {
+        if (g.empty() || g.size() > ZARC_GPU_SEARCH_MAX_PATTERN) { std::fprintf(stderr, "Error: the pattern has 1 to %d bytes\n", ZARC_GPU_SEARCH_MAX_PATTERN); return 2; }
+        if (lines_mode && !tally && g.find('\n') != std::string::npos) { std::fprintf(stderr, "Error: the pattern must not contain a newline when lines are asked for\n"); return 2; }
     }
-    if (pattern.empty() || pattern.size() > ZARC_GPU_SEARCH_MAX_PATTERN) { std::fprintf(stderr, "Error: the pattern has 1 to %d bytes\n", ZARC_GPU_SEARCH_MAX_PATTERN); return 2; }
-    if (lines_mode && pattern.find('\n') != std::string::npos) { std::fprintf(stderr, "Error: the pattern must not contain a newline when lines are asked for\n"); return 2; }
+    pattern = given[0];
+    // a set: patterns that are equal after folding are searched once; slot_of[k] = where the k-th given pattern lies in the set
+    std::vector<std::string> set;
+    std::vector<size_t> slot_of;
+    if (use_set) {
+        std::map<std::string, size_t> seen;
+        for (const std::string &g : given) {
+            std::string key = g;
+            if (icase) for (char &ch : key) if (ch >= 'A' && ch <= 'Z') ch = (char)(ch | 0x20);
+            auto it = seen.find(key);
+            if (it == seen.end()) { it = seen.emplace(key, set.size()).first; set.push_back(g); }
+            slot_of.push_back(it->second);
+        }
+        if (set.size() > ZARC_GPU_SEARCH_MAX_SET) { std::fprintf(stderr, "Error: a set has at most %d different patterns\n", ZARC_GPU_SEARCH_MAX_SET); return 2; }
+        if (tally) lines_mode = false; // the tally replaces the per-file output: the counting pass gives it
+    }
     try {
         if (gpus > zarc_gpu_device_count()) { std::fprintf(stderr, "Error: --gpus %d but %d device(s) are usable\n", gpus, zarc_gpu_device_count()); return 2; }
         Mapped m(input);
@@ -826,7 +876,8 @@ int cmd_grep(const std::vector<std::string> &a)
                 for (size_t batch_bytes = 0; at + batch.size() < todo.size() && batch_bytes < BATCH; batch_bytes += (size_t)rd.frames().at(batch.back()).uncompressed)
                     batch.push_back(todo[at + batch.size()]);
                 std::vector<zarc::FrameReader::Result> res =
-                    rd.search_lines(batch, pattern, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0);
+                    use_set ? rd.search_set_lines(batch, set, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0)
+                            : rd.search_lines(batch, pattern, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0);
                 LOGF(3, "search_lines", "frames=%zu", batch.size());
                 size_t taken = batch.size();
                 for (size_t k = 0; k < batch.size(); k++) {
@@ -877,9 +928,12 @@ int cmd_grep(const std::vector<std::string> &a)
         const size_t BATCH = (size_t)1 << 30;
         std::vector<zarc::Digest> batch;
         size_t batch_bytes = 0;
+        std::vector<uint64_t> set_hits(set.size(), 0); // --tally: per pattern of the set, over every batch
         auto flush = [&]() {
             if (batch.empty()) return;
-            const std::vector<zarc::FrameReader::Result> res = rd.search_frames(batch, pattern, icase);
+            std::vector<uint64_t> batch_hits;
+            const std::vector<zarc::FrameReader::Result> res = use_set ? rd.search_set(batch, set, icase, tally ? &batch_hits : nullptr) : rd.search_frames(batch, pattern, icase);
+            for (size_t k = 0; k < batch_hits.size(); k++) set_hits[k] += batch_hits[k];
             for (size_t k = 0; k < batch.size(); k++) {
                 const bool decoded = res[k].status == ZARC_GPU_FRAME_OK || res[k].status == ZARC_GPU_FRAME_DIGEST;
                 for (size_t i : files_of[batch[k]]) {
@@ -902,6 +956,11 @@ int cmd_grep(const std::vector<std::string> &a)
             if (batch_bytes >= BATCH) flush();
         }
         flush();
+        if (tally) {
+            for (size_t k = 0; k < typed.size(); k++) std::printf("%llu\t%s\n", (unsigned long long)set_hits[slot_of[k]], typed[k].c_str());
+            matched = hits.size();
+            hits.clear();
+        }
         for (const auto &kv : hits) {
             const std::string path = to_path(rd.files()[kv.first].name);
             if (names_only) std::printf("%s\n", path.c_str());

@@ -459,6 +459,32 @@ class ArchiveReader {
         }
         return reader_.lines_content_frames(data_, len_, wanted, pattern, icase, max_lines, max_line, rec_cap);
     }
+    // search_frames for a set of fixed byte strings in one pass (FrameReader::search_set_content_frames): count, first and which of the
+    // union per digest, in order; hits (may be null) receives the per-pattern sums over these frames
+    std::vector<FrameReader::Result> search_set(const std::vector<Digest> &digests, const std::vector<std::string> &patterns, bool icase = false,
+                                                std::vector<uint64_t> *hits = nullptr)
+    {
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.search_set_content_frames(data_, len_, wanted, patterns, icase, hits);
+    }
+    // ... and search_lines for a set (FrameReader::lines_set_content_frames)
+    std::vector<FrameReader::Result> search_set_lines(const std::vector<Digest> &digests, const std::vector<std::string> &patterns, bool icase = false,
+                                                      uint64_t max_lines = 0, uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20,
+                                                      std::vector<uint64_t> *hits = nullptr)
+    {
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.lines_set_content_frames(data_, len_, wanted, patterns, icase, max_lines, max_line, rec_cap, hits);
+    }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()
     {

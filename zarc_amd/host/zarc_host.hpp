@@ -373,6 +373,7 @@ class FrameReader {
         int status = ZARC_GPU_FRAME_OK;  // Error::Zstd analogue (decode/error.rs:35-38) via zarc_gpu_frame_status_name
         uint64_t count = 0;              // search_content_frames: start positions at which the pattern occurs (0 for a frame that did not decode)
         std::optional<uint64_t> first;   // ... and the lowest of them
+        std::optional<uint64_t> which;   // search_set_content_frames: the lowest index of a pattern that matches at `first`
         // lines_content_frames: the frame's matching lines, all of them counted, and the records of those that were delivered (they own their bytes)
         struct Line { uint64_t start, length, number, match; std::vector<uint8_t> text; }; // zarc_gpu_line; text: the line's first min(length, max_line) bytes
         uint64_t lines = 0;
@@ -431,8 +432,53 @@ class FrameReader {
         return out;
     }
 
+    // search_content_frames for a SET of 1 .. ZARC_GPU_SEARCH_MAX_SET fixed byte strings in one pass (zarc_gpu_search_set_batch): count is the
+    // start positions at which at least one pattern matches, first the lowest of them, which the lowest index of a pattern matching there.
+    // hits (may be null) receives, per pattern, the positions at which it matches, summed over the frames that were searched -- over all
+    // handles: the sums and everything else are identical for every number of handles.
+    std::vector<Result> search_set_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted,
+                                                  const std::vector<std::string> &patterns, bool icase = false, std::vector<uint64_t> *hits = nullptr)
+    {
+        check_set(patterns, false);
+        Search s{nullptr, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u};
+        s.set = &patterns; s.hits = hits;
+        if (hits) hits->assign(patterns.size(), 0);
+        return run_frames(archive, archive_len, wanted, false, &s);
+    }
+    // lines_content_frames for a set (zarc_gpu_search_set_lines_batch): a line matches when a match of any pattern starts in it, a
+    // record's `match` is the lowest such position.  No pattern may contain 0x0A.
+    std::vector<Result> lines_set_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted,
+                                                 const std::vector<std::string> &patterns, bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096,
+                                                 size_t rec_cap = (size_t)1 << 20, std::vector<uint64_t> *hits = nullptr)
+    {
+        check_set(patterns, true);
+        if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) throw Error(ZARC_GPU_E_PARAM, "max_line is 1 to 65536");
+        Search s{nullptr, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, true, max_lines, max_line, rec_cap};
+        s.set = &patterns; s.hits = hits;
+        if (hits) hits->assign(patterns.size(), 0);
+        std::vector<Result> out = run_frames(archive, archive_len, wanted, false, &s);
+        size_t left = rec_cap;
+        for (Result &r : out) { // the delivery rule over the merged list, as in lines_content_frames
+            if (r.line_records.size() > left) r.line_records.resize(left);
+            left -= r.line_records.size();
+        }
+        return out;
+    }
+
   private:
-    struct Search { const std::string *pattern; unsigned flags; bool lines = false; uint64_t max_lines = 0, max_line = 0; size_t rec_cap = 0; };
+    struct Search {
+        const std::string *pattern; unsigned flags; bool lines = false; uint64_t max_lines = 0, max_line = 0; size_t rec_cap = 0;
+        const std::vector<std::string> *set = nullptr; // a set of patterns in place of the one
+        std::vector<uint64_t> *hits = nullptr;         // ... and its per-pattern sums over all handles
+    };
+    static void check_set(const std::vector<std::string> &patterns, bool lines)
+    {
+        if (patterns.empty() || patterns.size() > ZARC_GPU_SEARCH_MAX_SET) throw Error(ZARC_GPU_E_PARAM, "a set has 1 to 1024 patterns");
+        for (const std::string &p : patterns) {
+            if (p.empty() || p.size() > ZARC_GPU_SEARCH_MAX_PATTERN) throw Error(ZARC_GPU_E_PARAM, "a pattern has 1 to 256 bytes");
+            if (lines && p.find('\n') != std::string::npos) throw Error(ZARC_GPU_E_PARAM, "a pattern must not contain a newline");
+        }
+    }
     std::vector<Result> run_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, bool with_data, const Search *search = nullptr)
     {
         const size_t n = wanted.size();
@@ -447,6 +493,16 @@ class FrameReader {
         const size_t g = engines_.size();
         const auto share = shard_assign(rl.data(), n, g);
         std::vector<int> rc(g, ZARC_GPU_OK);
+        // a set of patterns: one image for all handles, and every handle's own hits
+        std::string set_bytes;
+        std::vector<uint64_t> set_off, set_len;
+        size_t shortest = search && search->pattern ? search->pattern->size() : 1;
+        if (search && search->set) {
+            shortest = SIZE_MAX;
+            for (const std::string &p : *search->set) { set_off.push_back(set_bytes.size()); set_len.push_back(p.size()); set_bytes += p; shortest = std::min(shortest, p.size()); }
+        }
+        const zarc_gpu_pattern_set pset{set_bytes.data(), set_off.data(), set_len.data(), set_off.size()};
+        std::vector<std::vector<uint64_t>> share_hits(g);
         auto unpack_share = [&](size_t d) {
             const std::vector<size_t> &idx = share[d];
             const size_t m = idx.size();
@@ -456,7 +512,8 @@ class FrameReader {
             std::vector<size_t> fl(m), ul(m);
             std::vector<Digest> expect(m), got(m);
             std::vector<int> status(m);
-            std::vector<uint64_t> count(search ? m : 0), first(search ? m : 0);
+            std::vector<uint64_t> count(search ? m : 0), first(search ? m : 0), which(search && search->set ? m : 0);
+            if (search && search->set) share_hits[d].assign(set_off.size(), 0);
             for (size_t j = 0; j < m; j++) {
                 const Frame &f = wanted[idx[j]];
                 fp[j] = archive + f.offset; fl[j] = f.length; ul[j] = f.uncompressed; dp[j] = out[idx[j]].data.data(); expect[j] = f.digest;
@@ -469,13 +526,21 @@ class FrameReader {
             size_t rec_cap = 0, rec_used = 0, text_used = 0;
             if (search && search->lines) {
                 uint64_t room = 0;
-                for (size_t j = 0; j < m; j++) room += ul[j] / search->pattern->size() + 1;
+                for (size_t j = 0; j < m; j++) room += ul[j] / shortest + 1;
                 rec_cap = (size_t)std::min<uint64_t>(search->rec_cap, room);
                 nlines.resize(m); rec.resize(rec_cap);
                 text.reset((uint8_t *)std::malloc(std::max<size_t>(1, rec_cap * (size_t)search->max_line)));
                 if (!text) { rc[d] = ZARC_GPU_E_NOMEM; return; }
             }
-            rc[d] = search && search->lines
+            rc[d] = search && search->set && search->lines
+                        ? zarc_gpu_search_set_lines_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), &pset,
+                                                          search->flags, search->max_lines, search->max_line, (uint8_t(*)[32])got.data(), status.data(), count.data(),
+                                                          first.data(), which.data(), share_hits[d].data(), nlines.data(), rec.data(), rec_cap, &rec_used, text.get(),
+                                                          rec_cap * (size_t)search->max_line, &text_used)
+                    : search && search->set
+                        ? zarc_gpu_search_set_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), &pset, search->flags,
+                                                    (uint8_t(*)[32])got.data(), status.data(), count.data(), first.data(), which.data(), share_hits[d].data())
+                    : search && search->lines
                         ? zarc_gpu_search_lines_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
                                                       search->pattern->data(), search->pattern->size(), search->flags, search->max_lines, search->max_line,
                                                       (uint8_t(*)[32])got.data(), status.data(), count.data(), first.data(), nlines.data(), rec.data(), rec_cap,
@@ -496,6 +561,7 @@ class FrameReader {
                 if (decoded) r.verify = got[j] == expect[j]; // a mismatch is reported, not fatal (zarc-cli/src/unpack.rs:118-120)
                 else r.data.clear();
                 if (search) { r.count = count[j]; if (first[j] != ZARC_GPU_SEARCH_NONE) r.first = first[j]; }
+                if (search && search->set && which[j] != ZARC_GPU_SEARCH_NONE) r.which = which[j];
                 if (search && search->lines) r.lines = nlines[j];
             }
             for (size_t k = 0; k < rec_used; k++) {
@@ -510,6 +576,9 @@ class FrameReader {
             for (auto &t : th) t.join();
         }
         for (size_t d = 0; d < g; d++) engines_[d]->check(rc[d]);
+        if (search && search->hits)
+            for (const std::vector<uint64_t> &sh : share_hits)
+                for (size_t k = 0; k < sh.size(); k++) (*search->hits)[k] += sh[k];
         return out;
     }
 
