@@ -45,7 +45,8 @@ extern "C" {
                                   that wants them at the symbol lookup, not by version.  zarc_gpu_repack_batch* joined them the same way, for the
                                   same reason, and zarc_gpu_search_batch* with ZARC_GPU_T_SEARCH after them (ZARC_GPU_T_COUNT grew from 10 to 11:
                                   zarc_gpu_last_kernel_ms of an older library answers < 0 for the new id, as for any id it does not know), and
-                                  zarc_gpu_search_lines_batch* with ZARC_GPU_T_LINES after those (ZARC_GPU_T_COUNT grew from 11 to 12) */
+                                  zarc_gpu_search_lines_batch* with ZARC_GPU_T_LINES after those (ZARC_GPU_T_COUNT grew from 11 to 12), then
+                                  zarc_gpu_search_set_*, and zarc_gpu_regex_compile with zarc_gpu_search_regex_* (new symbols; ZARC_GPU_T_COUNT stays 12) */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -406,6 +407,63 @@ int zarc_gpu_search_set_lines_batch_device(zarc_gpu_t *h, size_t n, const void *
                                            zarc_gpu_line *rec /* HOST array */, size_t rec_cap, size_t *rec_used, void *d_text /* DEVICE pointer */,
                                            size_t text_cap, size_t *text_used);
 
+/* ---- search, a regular expression: matched on the device, line by line ------------------------------------------------------------------ */
+/* What `grep -E` answers: zarc_gpu_search_batch* and zarc_gpu_search_lines_batch* with a regular expression in place of the fixed string.
+ * Matching is per LINE (as zarc_gpu_search_lines_batch defines a line) and never crosses a 0x0A or a frame's end; the frame's first byte
+ * starts a line and the frame's end ends one, with or without a final 0x0A; a 0x0D in front of a 0x0A is part of the line (`x$` does not
+ * match "x\r\n", as in grep).
+ *   - Position p is a MATCHING START POSITION of regex R when some non-empty run content[p .. j) inside p's line is in L(R); `^` holds only
+ *     at the line's first byte, `$` only behind its last.  Whether a match exists at p does not depend on leftmost-longest or backtracking
+ *     order, so POSIX, Python's `re` and this engine agree on it: per line it is {m.start() for m in re.finditer(b"(?=(?:R))", line)}.
+ *   - count[i] = the number of matching start positions of frame i, first[i] = the lowest or ZARC_GPU_SEARCH_NONE.  The lines forms are
+ *     zarc_gpu_search_lines_batch* word for word with this meaning of "matching start position" (rec.match: the lowest in the line).  A regex
+ *     that is one literal string gives exactly the fixed-string call's answers.
+ *   - Dialect: bytes, POSIX ERE's operators with Python's escapes.  Literals; `.` (any byte but 0x0A, 0x00 and bytes >= 0x80 included);
+ *     `[...]` `[^...]` with ranges (`]` first is the byte); `( )`; `|`; `*` `+` `?` `{n}` `{n,}` `{n,m}` with n <= m <= 255; `^` `$`.
+ *     Escapes, outside and inside brackets alike: `\` + punctuation = that byte; \t \r \f \v \0 \xHH; \d \D \w \W \s \S (ASCII).  No class ever
+ *     matches 0x0A: negated classes, \s \D \W \S silently lose it.  ZARC_GPU_SEARCH_ICASE folds ASCII letters only, in literals and classes.
+ *   - ZARC_GPU_E_PARAM, zarc_gpu_last_error() = "regex: offset N: reason" with N the byte offset in the regex: unbalanced ( ) [; a quantifier
+ *     with nothing to repeat or on a quantifier; a `{` that is not a valid bound, {3,2}, {,m}, a bound above 255; [b-a]; an empty regex or
+ *     one above ZARC_GPU_REGEX_MAX_PATTERN bytes; any other `\` + letter or digit (\b \1 \A ...: no back-references, word boundaries,
+ *     look-around); lazy and possessive quantifiers (*? ++); a literal 0x0A, \n or \x0a; a regex that can match without consuming a content
+ *     byte, anchors counted as empty (a*, x|, (), ^$): it would match every line and no position could carry the match.
+ *   - ZARC_GPU_E_UNSUPPORTED, the message giving the states needed: the minimised automaton has more than ZARC_GPU_REGEX_MAX_STATES states.
+ *     This is inherent to answering "does a match START here": the automaton is that of SIGMA* . reverse(R), read from a line's last byte
+ *     to its first, and .{k}a needs 2^(k+1) states (.{4}a fits, .{7}a does not); a literal of m bytes needs m + 1.  Raising the constant is
+ *     a known follow-up: the kernels' LDS arrays that scale with it are `delta` (states x 256 bytes) and `tab` (256 threads x states
+ *     bytes) of zdec_regex.hip, 16 KiB each at 64; the tables store a state in one byte, which holds up to 256 of them.
+ *   - The compiled table (zarc_gpu_regex_compile, public and handle-less so that a caller can refuse a bad expression before it opens
+ *     anything): delta[q * 256 + byte] for q < states; start = the state at a line's end; accept[q] bit 0 = a match starts at the byte just
+ *     read, bit 1 = a match starts there if it is the line's first byte.  delta[q][0x0A] == start for every q and accept[start] == 0.
+ *   - Everything that is not matching is zarc_gpu_search_batch's / zarc_gpu_search_lines_batch's: status, digest, which frames are searched,
+ *     the missing-array checks, n == 0 (the regex is validated all the same), the 4 GiB rule, ZARC_GPU_PX_SCRATCH_MB and parts,
+ *     zarc_gpu_last_copy_bytes (the compiled table is not content), zarc_gpu_last_kernel_ms (ZARC_GPU_T_SEARCH: zarc_regex_summary,
+ *     zarc_regex_carry, zarc_regex_scan; ZARC_GPU_T_LINES: the line kernels).
+ *   - Cost: one dependent LDS lookup per content byte per pass (summary and scan; mark and emit for lines).  A 256-byte chunk without a
+ *     0x0A (binaries) pays up to `states` lookups per byte for its transition table instead -- slower, but parallel: no lane ever walks
+ *     more than its 256 bytes times `states`, whatever the line length. */
+#define ZARC_GPU_REGEX_MAX_PATTERN 1024
+#define ZARC_GPU_REGEX_MAX_STATES 64
+typedef struct { uint32_t states; uint32_t start; uint8_t accept[64]; uint8_t delta[64 * 256]; } zarc_gpu_regex_dfa;
+/* 0, ZARC_GPU_E_PARAM or ZARC_GPU_E_UNSUPPORTED; err (may be NULL) receives the text zarc_gpu_last_error would give ("" on success) */
+int zarc_gpu_regex_compile(const void *regex, size_t regex_len, unsigned flags, zarc_gpu_regex_dfa *out /* may be NULL */, char *err, size_t err_cap);
+int zarc_gpu_search_regex_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const void *regex, size_t regex_len, unsigned flags,
+                                uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first);
+int zarc_gpu_search_regex_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                       const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const void *regex /* HOST pointer */,
+                                       size_t regex_len, unsigned flags, uint8_t *digest /* n*32 */, int *status, uint64_t *count, uint64_t *first);
+int zarc_gpu_search_regex_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                      const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const void *regex, size_t regex_len, unsigned flags,
+                                      uint64_t max_lines /* per frame; 0 = no limit */, uint64_t max_line /* 1..65536 */,
+                                      uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *lines /* n */,
+                                      zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *text, size_t text_cap, size_t *text_used);
+int zarc_gpu_search_regex_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                             const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const void *regex /* HOST pointer */,
+                                             size_t regex_len, unsigned flags, uint64_t max_lines, uint64_t max_line, uint8_t *digest /* n*32 */,
+                                             int *status, uint64_t *count, uint64_t *first, uint64_t *lines, zarc_gpu_line *rec /* HOST array */,
+                                             size_t rec_cap, size_t *rec_used, void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
+
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN]);
@@ -430,8 +488,8 @@ enum {
     ZARC_GPU_T_DEC_SEQS = 7,  /* decoder stage 2: sequence entropy decoding (zarc_zdec_seqs)             */
     ZARC_GPU_T_DEC_LITS = 8,  /* decoder stage 2: Huffman literals (zarc_zdec_literals, side stream)      */
     ZARC_GPU_T_DEC_FRAMES = 9,/* decoder frame pass (zarc_zstd_frames + the inline decoder for the rest)  */
-    ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan (a set: zarc_set_scan and zarc_set_which), summed over the parts of a call; < 0 or 0 after any other call */
-    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set: its twins of mark and emit), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan (a set: zarc_set_scan and zarc_set_which; a regex: zarc_regex_summary, _carry and _scan), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set or a regex: its twins of mark and emit), summed over the parts of a call; < 0 or 0 after any other call */
     ZARC_GPU_T_COUNT = 12
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);

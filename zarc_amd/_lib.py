@@ -39,6 +39,7 @@ T_LINES = 11   # zarc_lines_* of a search_lines call (summed over its parts)
 SEARCH_ICASE, SEARCH_MAX_PATTERN, SEARCH_NONE = 1, 256, 2 ** 64 - 1
 SEARCH_MAX_SET = 1024  # zarc_gpu_search_set_*: the largest set
 LINES_MAX_LINE = 65536  # zarc_gpu_search_lines_batch*: the largest max_line
+REGEX_MAX_PATTERN, REGEX_MAX_STATES = 1024, 64  # zarc_gpu_search_regex_*: the longest expression, the most states of its automaton
 
 EXPORTS = [
     "zarc_gpu_abi_version", "zarc_gpu_level_finder", "zarc_gpu_parameter_advisory", "zarc_gpu_device_count", "zarc_gpu_create", "zarc_gpu_destroy", "zarc_gpu_set_parameter", "zarc_gpu_get_params",
@@ -47,6 +48,8 @@ EXPORTS = [
     "zarc_gpu_verify_batch", "zarc_gpu_verify_batch_device", "zarc_gpu_last_copy_bytes", "zarc_gpu_repack_batch", "zarc_gpu_repack_batch_device",
     "zarc_gpu_search_batch", "zarc_gpu_search_batch_device", "zarc_gpu_search_lines_batch", "zarc_gpu_search_lines_batch_device",
     "zarc_gpu_search_set_batch", "zarc_gpu_search_set_batch_device", "zarc_gpu_search_set_lines_batch", "zarc_gpu_search_set_lines_batch_device",
+    "zarc_gpu_regex_compile", "zarc_gpu_search_regex_batch", "zarc_gpu_search_regex_batch_device", "zarc_gpu_search_regex_lines_batch",
+    "zarc_gpu_search_regex_lines_batch_device",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -85,6 +88,11 @@ class PatternSet(ctypes.Structure):
             at += len(p)
         s.bytes, s.off, s.len, s.count = ctypes.cast(s._blob, ctypes.c_void_p), s._off, s._len, n
         return s
+
+
+class RegexDfa(ctypes.Structure):
+    """zarc_gpu_regex_dfa: the table zarc_gpu_regex_compile makes; it reads a line from its last byte to its first"""
+    _fields_ = [("states", ctypes.c_uint32), ("start", ctypes.c_uint32), ("accept", ctypes.c_uint8 * 64), ("delta", ctypes.c_uint8 * (64 * 256))]
 
 
 class ZarcGpuError(RuntimeError):
@@ -148,6 +156,11 @@ def load(path=None):
                                                     szp, vp, sz, szp]
     lib.zarc_gpu_search_set_lines_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, sp, c.c_uint, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, u64p, u64p,
                                                            lp, sz, szp, vp, sz, szp]
+    lib.zarc_gpu_regex_compile.argtypes = [vp, sz, c.c_uint, c.POINTER(RegexDfa), c.c_char_p, sz]
+    lib.zarc_gpu_search_regex_batch.argtypes = lib.zarc_gpu_search_batch.argtypes
+    lib.zarc_gpu_search_regex_batch_device.argtypes = lib.zarc_gpu_search_batch_device.argtypes
+    lib.zarc_gpu_search_regex_lines_batch.argtypes = lib.zarc_gpu_search_lines_batch.argtypes
+    lib.zarc_gpu_search_regex_lines_batch_device.argtypes = lib.zarc_gpu_search_lines_batch_device.argtypes
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

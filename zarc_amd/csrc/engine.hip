@@ -8,9 +8,11 @@
 // data-path byte is hashed, matched, coded and decoded by the gfx950 kernels.
 #include "../../include/zarc_gpu.h"
 #include "zarc_kernels.h"
+#include "zre_compile.h" // the regular-expression compiler (host code)
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -118,6 +120,8 @@ struct zarc_gpu {
     // a set of patterns (zarc_gpu_search_set_*): zarc_set_scan / zarc_set_which in place of zarc_search_scan
     DevBuf d_set, d_set_hits, d_set_which;      // the compiled set (search_upload_set); hits of every pattern in this part; lowest matching pattern of every frame (decoder order)
     ZarcSetDesc set_desc{};                     // where things lie in d_set
+    // a regular expression (zarc_gpu_search_regex_*): zarc_regex_* in place of zarc_search_scan
+    DevBuf d_regex, d_re_summary, d_re_entry;   // the compiled table (search_upload_regex); ZarcRegexSlice and entry state of every slice of this part
     // the matching lines of a search (zarc_gpu_search_lines_batch*): zarc_lines_* behind zarc_search_scan, per part
     DevBuf d_ln_slices, d_ln_lines;             // ZarcLineSlice of every slice; matching lines of every frame (decoder order)
     DevBuf d_ln_base, d_ln_deliver;             // what the host decided: first record and number of records of every frame (decoder order)
@@ -655,6 +659,8 @@ struct SearchReq {
     const ZarcSetDesc *set = nullptr; // the handle's, made by search_upload_set; the blob is h->d_set
     uint64_t *which = nullptr; // host, in the caller's order: the lowest pattern that matches at first[i], or ZARC_GPU_SEARCH_NONE
     uint64_t *hits = nullptr;  // host, per pattern, or null: every part ADDS the positions at which the pattern matches in its frames
+    // a regular expression in place of the pattern (zarc_gpu_search_regex_*): d_pattern and m are not looked at
+    const ZarcRegexDfa *d_regex = nullptr; // device: the handle's table, made by search_upload_regex
 };
 int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
 static_assert(sizeof(ZarcLineRec) == sizeof(zarc_gpu_line), "the device's record is the caller's");
@@ -1546,8 +1552,20 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
             ZHIP(h->d_set_which.reserve(n * 4));
             if (srch->hits) ZHIP(hipMemsetAsync(h->d_set_hits.p, 0, (size_t)srch->set->count * 4, h->stream)); // (reserved by search_upload_set)
         }
+        if (srch->d_regex) {
+            ZHIP(h->d_re_summary.reserve(slices[n] * sizeof(ZarcRegexSlice)));
+            ZHIP(h->d_re_entry.reserve(slices[n]));
+        }
         ZHIP(t.mark(&e5));
-        if (srch->set) {
+        if (srch->d_regex) { // what every slice does to the state, every slice's entry state from the frame's end down, then the scan
+            hipLaunchKernelGGL(zarc_regex_summary, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_regex, h->d_re_summary.as<ZarcRegexSlice>());
+            hipLaunchKernelGGL(zarc_regex_carry, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(),
+                               h->d_status.as<int32_t>(), srch->d_regex, h->d_re_summary.as<ZarcRegexSlice>(), h->d_re_entry.as<uint8_t>());
+            hipLaunchKernelGGL(zarc_regex_scan, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_regex, h->d_re_entry.as<uint8_t>(),
+                               h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>());
+        } else if (srch->set) {
             hipLaunchKernelGGL(zarc_set_scan, dim3((unsigned)slices[n]), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
                                b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase,
                                h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>(), srch->hits ? h->d_set_hits.as<uint32_t>() : (uint32_t *)nullptr);
@@ -1564,7 +1582,11 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         if (srch->ln) { // ---- lines, first half: what every slice holds, what every slice must know of its neighbours, lines[] of every frame
             ZHIP(h->d_ln_slices.reserve(slices[n] * sizeof(ZarcLineSlice)));
             ZHIP(h->d_ln_lines.reserve(n * 4));
-            if (srch->set)
+            if (srch->d_regex)
+                hipLaunchKernelGGL(zarc_lines_mark_regex, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                                   b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_regex, h->d_re_entry.as<uint8_t>(),
+                                   h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
+            else if (srch->set)
                 hipLaunchKernelGGL(zarc_lines_mark_set, dim3((unsigned)slices[n]), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
                                    b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase,
                                    h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
@@ -1632,7 +1654,11 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
             ZHIP(hipMemsetAsync(h->d_ln_rec.p, 0, nrec * sizeof(ZarcLineRec), h->stream)); // (a record nobody wrote would name no frame and no text)
             int e8, e9;
             ZHIP(t.mark(&e8));
-            if (srch->set)
+            if (srch->d_regex)
+                hipLaunchKernelGGL(zarc_lines_emit_regex, dim3((unsigned)slices_total), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
+                                   b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), srch->d_regex, h->d_re_entry.as<uint8_t>(), h->d_ln_slices.as<ZarcLineSlice>(),
+                                   h->d_ln_base.as<uint64_t>(), h->d_ln_deliver.as<uint32_t>(), ln.max_line, h->d_ln_rec.as<ZarcLineRec>());
+            else if (srch->set)
                 hipLaunchKernelGGL(zarc_lines_emit_set, dim3((unsigned)slices_total), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
                                    b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase, h->d_ln_slices.as<ZarcLineSlice>(),
                                    h->d_ln_base.as<uint64_t>(), h->d_ln_deliver.as<uint32_t>(), ln.max_line, h->d_ln_rec.as<ZarcLineRec>());
@@ -1842,13 +1868,14 @@ int lines_check_args(zarc_gpu_t *h, const void *pattern, size_t pattern_len, uin
 // one part of a lines call (the whole of the device form, a chunk of the host form): search's pass with the line kernels behind it
 int search_lines_part(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, const uint64_t *raw_len,
                       const uint8_t *expect, size_t pattern_len, unsigned flags, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, const LinesReq &ln,
-                      uint64_t *which = nullptr, uint64_t *hits = nullptr) // which: the handle's set (search_upload_set) in place of its pattern
+                      uint64_t *which = nullptr, uint64_t *hits = nullptr, bool regex = false) // which: the handle's set (search_upload_set) in place of its pattern; regex: its table (search_upload_regex)
 {
     int rc = check_common(h, n);
     if (rc) return rc;
     SearchReq srch{h->d_srch_pat.as<uint8_t>(), (uint32_t)pattern_len, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
     srch.ln = &ln;
     if (which) { srch.set = &h->set_desc; srch.which = which; srch.hits = hits; }
+    if (regex) srch.d_regex = h->d_regex.as<ZarcRegexDfa>();
     return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
 }
 } // namespace
@@ -1997,6 +2024,85 @@ int zarc_gpu_search_set_lines_batch_device(zarc_gpu_t *h, size_t n, const void *
     LinesRun run;
     const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, (uint8_t *)d_text, nullptr, &run};
     rc = search_lines_part(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, 0, flags, digest, status, count, first, ln, which, hits);
+    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
+    return rc;
+}
+} // extern "C"
+namespace {
+static_assert(sizeof(ZarcRegexDfa) == sizeof(zarc_gpu_regex_dfa) && offsetof(ZarcRegexDfa, delta) == offsetof(zarc_gpu_regex_dfa, delta), "the device's table is the caller's");
+// what every regex entry point checks the same way, before anything else is looked at (search_check_args for an expression), and the
+// table: compiled here, once per call -- a bad expression is refused whatever n is
+int search_regex_check_args(zarc_gpu_t *h, const void *regex, size_t regex_len, unsigned flags, const void *digest, const int *status, const uint64_t *count,
+                            const uint64_t *first, zarc_gpu_regex_dfa *dfa)
+{
+    if (!h) return ZARC_GPU_E_PARAM;
+    if (flags & ~(unsigned)ZARC_GPU_SEARCH_ICASE) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
+    std::string err;
+    const int rc = zre::compile(regex, regex_len, flags, dfa, err);
+    if (rc) { set_error(h, err.c_str()); return rc; }
+    if (!digest || !status || !count || !first) return ZARC_GPU_E_PARAM;
+    return 0;
+}
+int search_upload_regex(zarc_gpu_t *h, const zarc_gpu_regex_dfa *dfa)
+{
+    ZHIP(h->d_regex.reserve(sizeof *dfa));
+    ZHIP(hipMemcpy(h->d_regex.p, dfa, sizeof *dfa, hipMemcpyHostToDevice));
+    return 0;
+}
+} // namespace
+extern "C" {
+
+int zarc_gpu_regex_compile(const void *regex, size_t regex_len, unsigned flags, zarc_gpu_regex_dfa *out, char *err, size_t err_cap)
+{
+    std::string msg;
+    const int rc = zre::compile(regex, regex_len, flags, out, msg);
+    if (err && err_cap) { const size_t k = std::min(msg.size(), err_cap - 1); memcpy(err, msg.data(), k); err[k] = 0; }
+    return rc;
+}
+
+// zarc_gpu_search_batch_device with zarc_regex_summary, zarc_regex_carry and zarc_regex_scan in place of zarc_search_scan
+int zarc_gpu_search_regex_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                       const uint64_t *raw_len, const uint8_t *expect, const void *regex, size_t regex_len, unsigned flags,
+                                       uint8_t *digest, int *status, uint64_t *count, uint64_t *first)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (!h->nested) { // (the host form has compiled and uploaded the table for all its chunks)
+        zarc_gpu_regex_dfa dfa;
+        if ((rc = search_regex_check_args(h, regex, regex_len, flags, digest, status, count, first, &dfa))) return rc;
+        if (n == 0) return ZARC_GPU_OK;
+        if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
+        for (size_t i = 0; i < n; i++)
+            if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
+        if ((rc = search_upload_regex(h, &dfa))) return rc;
+    }
+    if (n == 0) return ZARC_GPU_OK;
+    SearchReq srch{nullptr, 0, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
+    srch.d_regex = h->d_regex.as<ZarcRegexDfa>();
+    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
+}
+
+// zarc_gpu_search_lines_batch_device with the automaton's kernels in place of the pattern's
+int zarc_gpu_search_regex_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                             const uint64_t *raw_len, const uint8_t *expect, const void *regex, size_t regex_len, unsigned flags,
+                                             uint64_t max_lines, uint64_t max_line, uint8_t *digest, int *status, uint64_t *count, uint64_t *first,
+                                             uint64_t *lines, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *d_text, size_t text_cap,
+                                             size_t *text_used)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    zarc_gpu_regex_dfa dfa;
+    if ((rc = search_regex_check_args(h, regex, regex_len, flags, digest, status, count, first, &dfa))) return rc;
+    if ((rc = lines_check_args(h, "", 0, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used))) return rc;
+    *rec_used = 0; *text_used = 0;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
+    for (size_t i = 0; i < n; i++)
+        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
+    if ((rc = search_upload_regex(h, &dfa))) return rc;
+    LinesRun run;
+    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, (uint8_t *)d_text, nullptr, &run};
+    rc = search_lines_part(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, 0, flags, digest, status, count, first, ln, nullptr, nullptr, true);
     *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
     return rc;
 }
@@ -2538,7 +2644,7 @@ namespace {
 int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                      const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const void *pattern,
                      size_t pattern_len, unsigned flags, uint64_t *count, uint64_t *first, const LinesReq *ln = nullptr,
-                     const zarc_gpu_pattern_set *set = nullptr, uint64_t *which = nullptr, uint64_t *hits = nullptr)
+                     const zarc_gpu_pattern_set *set = nullptr, uint64_t *which = nullptr, uint64_t *hits = nullptr, bool regex = false)
 {
     int rc = 0;
     if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
@@ -2586,8 +2692,12 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
             LinesReq sub = *ln;
             sub.lines += i0; sub.frame0 += i0;
             rc = search_lines_part(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0, expect ? (const uint8_t *)expect[i0] : nullptr,
-                                   pattern_len, flags, (uint8_t *)digest[i0], status + i0, count + i0, first + i0, sub, set ? which + i0 : nullptr, hits);
-        } else if (set)
+                                   pattern_len, flags, (uint8_t *)digest[i0], status + i0, count + i0, first + i0, sub, set ? which + i0 : nullptr, hits, regex);
+        } else if (regex) // (pattern, pattern_len: the expression; the nested call does not look at it, the handle's table is up)
+            rc = zarc_gpu_search_regex_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
+                                                    expect ? (const uint8_t *)expect[i0] : nullptr, pattern, pattern_len, flags, (uint8_t *)digest[i0], status + i0,
+                                                    count + i0, first + i0);
+        else if (set)
             rc = zarc_gpu_search_set_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
                                                   expect ? (const uint8_t *)expect[i0] : nullptr, set, flags, (uint8_t *)digest[i0], status + i0,
                                                   count + i0, first + i0, which + i0, hits);
@@ -2681,6 +2791,39 @@ int zarc_gpu_search_set_lines_batch(zarc_gpu_t *h, size_t n, const void *const *
     LinesRun run;
     const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, nullptr, (uint8_t *)text, &run};
     rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, 0, flags, count, first, &ln, set, which, hits);
+    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
+    return rc;
+}
+// zarc_gpu_search_batch's chunk loop with the automaton's kernels behind every chunk's verdict
+int zarc_gpu_search_regex_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *regex, size_t regex_len, unsigned flags,
+                                uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    zarc_gpu_regex_dfa dfa;
+    if ((rc = search_regex_check_args(h, regex, regex_len, flags, digest, status, count, first, &dfa))) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if ((rc = search_upload_regex(h, &dfa))) return rc;
+    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, regex, regex_len, flags, count, first, nullptr, nullptr, nullptr, nullptr, true);
+}
+// ... and with the line kernels behind every chunk's search
+int zarc_gpu_search_regex_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                      const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *regex, size_t regex_len, unsigned flags, uint64_t max_lines,
+                                      uint64_t max_line, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first,
+                                      uint64_t *lines, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *text, size_t text_cap, size_t *text_used)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    zarc_gpu_regex_dfa dfa;
+    if ((rc = search_regex_check_args(h, regex, regex_len, flags, digest, status, count, first, &dfa))) return rc;
+    if ((rc = lines_check_args(h, "", 0, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used))) return rc;
+    *rec_used = 0; *text_used = 0;
+    if (n == 0) return ZARC_GPU_OK;
+    if ((rc = search_upload_regex(h, &dfa))) return rc;
+    LinesRun run;
+    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, nullptr, (uint8_t *)text, &run};
+    rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, regex, regex_len, flags, count, first, &ln, nullptr, nullptr, nullptr, true);
     *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
     return rc;
 }

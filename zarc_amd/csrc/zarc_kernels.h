@@ -246,6 +246,24 @@ __global__ void zarc_lines_mark_set(uint32_t n, const uint64_t *slice_prefix, co
 __global__ void zarc_lines_emit_set(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
                                     ZarcSetDesc sd, const uint32_t *set, uint32_t icase, const ZarcLineSlice *slices, const uint64_t *rec_base,
                                     const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
+// a regular expression (zdec_regex.hip).  ZarcRegexDfa is zarc_gpu_regex_dfa, the table zre_compile.h makes: it reads a line from its last
+// byte to its first.  ZarcRegexSlice: what reading a slice from its last byte to its first does to the state -- a constant when the slice
+// holds a 0x0A (the automaton restarts there), else one exit state per entry state.  entry[s] (zarc_regex_carry): the state in front of
+// slice s's last byte; slices of frames of one slice have no record and no entry (their entry state is dfa->start).
+constexpr uint32_t ZARC_REGEX_MAX_STATES = 64;
+struct ZarcRegexDfa { uint32_t states, start; uint8_t accept[ZARC_REGEX_MAX_STATES]; uint8_t delta[ZARC_REGEX_MAX_STATES * 256]; };
+struct ZarcRegexSlice { uint8_t constant, value, pad[2]; uint8_t table[ZARC_REGEX_MAX_STATES]; };
+__global__ void zarc_regex_summary(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                   const int32_t *status, const ZarcRegexDfa *dfa, ZarcRegexSlice *summary);
+__global__ void zarc_regex_carry(uint32_t n, const uint64_t *slice_prefix, const int32_t *status, const ZarcRegexDfa *dfa, const ZarcRegexSlice *summary,
+                                 uint8_t *entry);
+__global__ void zarc_regex_scan(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                const int32_t *status, const ZarcRegexDfa *dfa, const uint8_t *entry, uint32_t *count, uint32_t *first);
+__global__ void zarc_lines_mark_regex(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                      const int32_t *status, const ZarcRegexDfa *dfa, const uint8_t *entry, ZarcLineSlice *slices, uint32_t *lines);
+__global__ void zarc_lines_emit_regex(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                      const ZarcRegexDfa *dfa, const uint8_t *entry, const ZarcLineSlice *slices, const uint64_t *rec_base,
+                                      const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

@@ -174,7 +174,7 @@ class Engine:
             dst_len.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
         return dst_off, dst_len, dig, status
 
-    def search_device(self, d_frames, frame_off, frame_len, raw_len, pattern, icase=False, expect=None):
+    def search_device(self, d_frames, frame_off, frame_len, raw_len, pattern, icase=False, expect=None, _fn="zarc_gpu_search_batch_device"):
         """verify_device plus a search of what was decoded, where it lies: -> list of (status, digest, count, first) per frame.
         `pattern` is a fixed byte string (host memory, 1..256 bytes); count = matching start positions, first = the lowest or None."""
         frame_off, pfo = _u64(frame_off)
@@ -188,14 +188,15 @@ class Engine:
         if expect is not None:
             exp = np.ascontiguousarray(expect, dtype=np.uint8)
         pat = bytes(pattern)
-        self._check(self.lib.zarc_gpu_search_batch_device(
+        self._check(getattr(self.lib, _fn)(
             self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
             ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0,
             dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
             count.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), first.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i])) for i in range(n)]
 
-    def search_lines_device(self, d_frames, frame_off, frame_len, raw_len, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+    def search_lines_device(self, d_frames, frame_off, frame_len, raw_len, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096,
+                            _fn="zarc_gpu_search_lines_batch_device"):
         """search_device plus the matching lines: -> (results, records) as search_lines() gives them.  The text is gathered into a device
         buffer of rec_cap * max_line bytes and copied back from there."""
         frame_off, pfo = _u64(frame_off)
@@ -215,7 +216,7 @@ class Engine:
         d_text = self.malloc(max(text_cap, 1))
         try:
             u64p = ctypes.POINTER(ctypes.c_uint64)
-            self._check(self.lib.zarc_gpu_search_lines_batch_device(
+            self._check(getattr(self.lib, _fn)(
                 self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
                 ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0, max_lines, max_line,
                 dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), count.ctypes.data_as(u64p), first.ctypes.data_as(u64p),
@@ -408,7 +409,7 @@ class Engine:
                                                    dig.ctypes.data_as(ctypes.c_void_p), status))
         return [(bytes(dig[i]), int(status[i])) for i in range(n)]
 
-    def search(self, frames, raw_lens, pattern, icase=False, expect=None):
+    def search(self, frames, raw_lens, pattern, icase=False, expect=None, _fn="zarc_gpu_search_batch"):
         """-> list of (status, digest, count, first) per frame: verify()'s verdict, the number of start positions at which the fixed byte
         string `pattern` (1..256 bytes; icase folds ASCII letters only) occurs in the frame's content, and the lowest of them (None without
         a match).  Only the compressed frames cross to the device; no content comes back."""
@@ -424,12 +425,12 @@ class Engine:
         if expect is not None:
             exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
         pat = bytes(pattern)
-        self._check(self.lib.zarc_gpu_search_batch(self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+        self._check(getattr(self.lib, _fn)(self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
                                                    ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0,
                                                    dig.ctypes.data_as(ctypes.c_void_p), status, count, first))
         return [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i])) for i in range(n)]
 
-    def search_lines(self, frames, raw_lens, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+    def search_lines(self, frames, raw_lens, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096, _fn="zarc_gpu_search_lines_batch"):
         """search() plus the lines that hold a match -> (results, records).  results[i] = (status, digest, count, first, lines): search()'s
         answer and the number of matching lines of frame i (all of them, whatever the caps).  records = [(frame, start, length, number,
         match, text_bytes)] ordered by (frame, start): per frame the first min(lines, max_lines or all) matching lines while rec_cap
@@ -451,12 +452,36 @@ class Engine:
         rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
         text_cap = rec_cap * max_line
         text = np.empty(max(text_cap, 1), dtype=np.uint8)
-        self._check(self.lib.zarc_gpu_search_lines_batch(
+        self._check(getattr(self.lib, _fn)(
             self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
             ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0, max_lines, max_line,
             dig.ctypes.data_as(ctypes.c_void_p), status, count, first, lines, rec, rec_cap, ctypes.byref(rec_used),
             text.ctypes.data_as(ctypes.c_void_p), text_cap, ctypes.byref(text_used)))
         return self._lines_result(n, status, dig, count, first, lines, rec, rec_used.value, bytes(text[:text_used.value]))
+
+    def search_regex(self, frames, raw_lens, regex, icase=False, expect=None):
+        """search() with a regular expression (include/zarc_gpu.h has the dialect) in place of the fixed string: count = the positions at
+        which a match starts inside its line, first = the lowest of them.  A bad expression raises with code E_PARAM, one whose automaton
+        needs more than 64 states with E_UNSUPPORTED."""
+        return self.search(frames, raw_lens, regex, icase, expect, _fn="zarc_gpu_search_regex_batch")
+
+    def search_regex_lines(self, frames, raw_lens, regex, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+        """search_lines() with a regular expression -> (results, records); a record's match is the lowest matching start of its line"""
+        return self.search_lines(frames, raw_lens, regex, icase, expect, max_lines, max_line, rec_cap, _fn="zarc_gpu_search_regex_lines_batch")
+
+    def search_regex_device(self, d_frames, frame_off, frame_len, raw_len, regex, icase=False, expect=None):
+        """search_device() with a regular expression (host memory)"""
+        return self.search_device(d_frames, frame_off, frame_len, raw_len, regex, icase, expect, _fn="zarc_gpu_search_regex_batch_device")
+
+    def search_regex_lines_device(self, d_frames, frame_off, frame_len, raw_len, regex, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+        """search_lines_device() with a regular expression (host memory)"""
+        return self.search_lines_device(d_frames, frame_off, frame_len, raw_len, regex, icase, expect, max_lines, max_line, rec_cap,
+                                        _fn="zarc_gpu_search_regex_lines_batch_device")
+
+    def regex_compile(self, regex, icase=False):
+        """-> (states, start, accept, delta): the table the device walks for `regex`, a line's bytes from the last to the first; accept and
+        delta are bytes objects of `states` and `states * 256` entries.  Raises as search_regex() does.  Needs no device."""
+        return regex_compile(self.lib, regex, icase)
 
     def search_set(self, frames, raw_lens, patterns, icase=False, expect=None):
         """search() for a set of 1..1024 fixed byte strings in ONE pass -> (results, hits).  results[i] = (status, digest, count, first,
@@ -530,3 +555,14 @@ class Engine:
                                                    dst.ctypes.data_as(ctypes.c_void_p), cap, dst_off, dst_len, dig.ctypes.data_as(ctypes.c_void_p), status))
         new = [bytes(dst[dst_off[i]:dst_off[i] + dst_len[i]]) if status[i] == _lib.FRAME_OK else None for i in range(n)]
         return new, [bytes(d) for d in dig], [int(x) for x in status]
+
+
+def regex_compile(lib, regex, icase=False):
+    """Engine.regex_compile without a handle: `lib` is what _lib.load() returns"""
+    pat = bytes(regex)
+    dfa = _lib.RegexDfa()
+    err = ctypes.create_string_buffer(512)
+    rc = lib.zarc_gpu_regex_compile(ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0, ctypes.byref(dfa), err, len(err))
+    if rc != _lib.OK:
+        raise _lib.ZarcGpuError(rc, lib.zarc_gpu_error_name(rc).decode(), err.value.decode("latin-1"))
+    return dfa.states, dfa.start, bytes(dfa.accept[:dfa.states]), bytes(dfa.delta[:dfa.states * 256])

@@ -198,6 +198,7 @@ int usage()
                          "       zarc grep [-i] [-l] [-b] [--hex] [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
                          "                 [--lines] [-n] [-c] [-a] [-m NUM] [--max-line BYTES] [--batch-lines N] PATTERN ARCHIVE\n"
                          "       zarc grep ... (-e PATTERN | -f FILE)... [--tally] ARCHIVE\n"
+                         "       zarc grep -E ... (PATTERN | (-e PATTERN | -f FILE)...) ARCHIVE\n"
                          "         searches the content of the files for PATTERN on the device, each distinct frame once, and writes nothing.  PATTERN is a\n"
                          "         fixed string of 1 to 256 bytes (grep -F), never a regular expression; --hex reads it as hex digits.  One line per file with\n"
                          "         a match: PATH:COUNT (overlapping occurrences count); -b adds :OFFSET of the first one, -l prints PATH alone, -i folds ASCII\n"
@@ -214,6 +215,11 @@ int usage()
                          "         line with matches of several is one line; the output is the same as for one PATTERN.  --tally prints, instead of the lines per\n"
                          "         file, one line COUNT<TAB>PATTERN per pattern in the order given (as typed; zeros included): the positions at which it matches,\n"
                          "         over the distinct frames searched\n"
+                         "         -E (--extended-regexp): PATTERN is a regular expression of up to 1024 bytes, matched on the device line by line -- POSIX ERE's\n"
+                         "         operators ( ) | * + ? {n,m} [...] . ^ $ with the escapes \\t \\r \\f \\v \\0 \\xHH \\d \\D \\w \\W \\s \\S; no back-references or word\n"
+                         "         boundaries.  COUNT is the number of positions at which a match starts; several -e and the lines of -f FILE are joined as\n"
+                         "         (A)|(B)|...  An expression that is refused, or whose automaton needs more than 64 states, ends the run with exit status 2\n"
+                         "         before ARCHIVE is opened.  --hex and --tally do not go with -E\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -742,7 +748,8 @@ int cmd_verify(const std::vector<std::string> &a)
 }
 
 // `zarc grep`: which files contain this byte string?  Every distinct content frame behind the files that pass the filters is decoded,
-// judged and searched on the device (zarc_gpu_search_batch; with -e / -f / --tally a set of strings in one pass, zarc_gpu_search_set_batch):
+// judged and searched on the device (zarc_gpu_search_batch; with -e / -f / --tally a set of strings in one pass, zarc_gpu_search_set_batch;
+// with -E a regular expression, zarc_gpu_search_regex_batch):
 // the compressed bytes go up, a few words per frame come back, and a frame that many files share is searched once.  Nothing is created, opened or changed in the file system.  Exit status: grep's.
 int cmd_grep(const std::vector<std::string> &a)
 {
@@ -754,6 +761,7 @@ int cmd_grep(const std::vector<std::string> &a)
     int gpus = 1;
     std::vector<std::string> typed; // -e / -f: the patterns of a set, as given
     bool use_set = false, tally = false;
+    bool ere = false; // -E: PATTERN is a regular expression (zarc_gpu_search_regex_batch*)
     for (size_t i = 0; i < a.size(); i++) {
         if (options && a[i] == "--filter" && i + 1 < a.size()) filters.emplace_back(a[++i]);
         else if (options && a[i] == "-e" && i + 1 < a.size()) { typed.push_back(a[++i]); use_set = true; }
@@ -778,13 +786,15 @@ int cmd_grep(const std::vector<std::string> &a)
         else if (options && a[i] == "--verify" && i + 1 < a.size()) verify = a[++i];
         else if (options && a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str());
         else if (options && a[i] == "--hex") hex = true;
+        else if (options && a[i] == "--extended-regexp") ere = true;
         else if (options && a[i] == "--") options = false;
         else if (options && a[i].size() >= 2 && a[i][0] == '-' && a[i][1] != '-') { // -i -l -b -F, alone or bundled
             for (size_t k = 1; k < a[i].size(); k++) {
                 if (a[i][k] == 'i') icase = true;
                 else if (a[i][k] == 'l') names_only = true;
                 else if (a[i][k] == 'b') with_offset = true;
-                else if (a[i][k] == 'F') {} // fixed strings are all there is
+                else if (a[i][k] == 'F') {} // fixed strings are the default
+                else if (a[i][k] == 'E') ere = true;
                 else if (a[i][k] == 'n') numbers = lines_mode = true;
                 else if (a[i][k] == 'c') count_lines = lines_mode = true;
                 else if (a[i][k] == 'a') as_text = lines_mode = true;
@@ -802,6 +812,18 @@ int cmd_grep(const std::vector<std::string> &a)
         if (typed.empty()) { std::fprintf(stderr, "Error: no pattern\n"); return 2; }
     } else typed.push_back(pattern);
     if (!have_pattern || input.empty() || gpus < 1 || gpus > 64) return usage();
+    if (ere) { // several expressions are one alternation, as in grep; a bad one is refused here, before the archive is opened
+        if (hex || tally) return usage();
+        std::string joined;
+        for (size_t k = 0; k < typed.size(); k++) joined += use_set ? (k ? "|(" : "(") + typed[k] + ")" : typed[k];
+        char why[256];
+        if (zarc_gpu_regex_compile(joined.data(), joined.size(), icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, nullptr, why, sizeof why) != ZARC_GPU_OK) {
+            std::fprintf(stderr, "Error: %s\n", why);
+            return 2;
+        }
+        typed.assign(1, joined);
+        use_set = false;
+    }
     std::vector<std::string> given = typed; // the patterns' bytes
     if (hex)
         for (std::string &g : given) {
@@ -814,6 +836,7 @@ int cmd_grep(const std::vector<std::string> &a)
             g = raw;
         }
     for (const std::string &g : given) {
+        if (ere) break; // (the compiler has judged it)
         if (g.empty() || g.size() > ZARC_GPU_SEARCH_MAX_PATTERN) { std::fprintf(stderr, "Error: the pattern has 1 to %d bytes\n", ZARC_GPU_SEARCH_MAX_PATTERN); return 2; }
         if (lines_mode && !tally && g.find('\n') != std::string::npos) { std::fprintf(stderr, "Error: the pattern must not contain a newline when lines are asked for\n"); return 2; }
     }
@@ -877,6 +900,7 @@ int cmd_grep(const std::vector<std::string> &a)
                     batch.push_back(todo[at + batch.size()]);
                 std::vector<zarc::FrameReader::Result> res =
                     use_set ? rd.search_set_lines(batch, set, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0)
+                    : ere   ? rd.search_regex_lines(batch, pattern, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0)
                             : rd.search_lines(batch, pattern, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0);
                 LOGF(3, "search_lines", "frames=%zu", batch.size());
                 size_t taken = batch.size();
@@ -932,7 +956,8 @@ int cmd_grep(const std::vector<std::string> &a)
         auto flush = [&]() {
             if (batch.empty()) return;
             std::vector<uint64_t> batch_hits;
-            const std::vector<zarc::FrameReader::Result> res = use_set ? rd.search_set(batch, set, icase, tally ? &batch_hits : nullptr) : rd.search_frames(batch, pattern, icase);
+            const std::vector<zarc::FrameReader::Result> res = use_set ? rd.search_set(batch, set, icase, tally ? &batch_hits : nullptr)
+                                                                : ere ? rd.search_regex(batch, pattern, icase) : rd.search_frames(batch, pattern, icase);
             for (size_t k = 0; k < batch_hits.size(); k++) set_hits[k] += batch_hits[k];
             for (size_t k = 0; k < batch.size(); k++) {
                 const bool decoded = res[k].status == ZARC_GPU_FRAME_OK || res[k].status == ZARC_GPU_FRAME_DIGEST;

@@ -485,6 +485,29 @@ class ArchiveReader {
         }
         return reader_.lines_set_content_frames(data_, len_, wanted, patterns, icase, max_lines, max_line, rec_cap, hits);
     }
+    // search_frames with a regular expression in place of the fixed string (FrameReader::search_regex_content_frames): matching is per line
+    std::vector<FrameReader::Result> search_regex(const std::vector<Digest> &digests, const std::string &regex, bool icase = false)
+    {
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.search_regex_content_frames(data_, len_, wanted, regex, icase);
+    }
+    // ... and search_lines with one (FrameReader::lines_regex_content_frames)
+    std::vector<FrameReader::Result> search_regex_lines(const std::vector<Digest> &digests, const std::string &regex, bool icase = false, uint64_t max_lines = 0,
+                                                        uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20)
+    {
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.lines_regex_content_frames(data_, len_, wanted, regex, icase, max_lines, max_line, rec_cap);
+    }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()
     {

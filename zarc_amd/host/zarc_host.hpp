@@ -465,12 +465,47 @@ class FrameReader {
         return out;
     }
 
+    // search_content_frames with a regular expression in place of the fixed string (zarc_gpu_search_regex_batch; include/zarc_gpu.h has the
+    // dialect): count is the positions at which a match starts inside its line, first the lowest of them.  A bad expression, or one whose
+    // automaton needs more than ZARC_GPU_REGEX_MAX_STATES states, throws with the compiler's message before any handle is used.
+    std::vector<Result> search_regex_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const std::string &regex,
+                                                    bool icase = false)
+    {
+        check_regex(regex, icase);
+        Search s{&regex, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u};
+        s.regex = true;
+        return run_frames(archive, archive_len, wanted, false, &s);
+    }
+    // ... and lines_content_frames with one (zarc_gpu_search_regex_lines_batch)
+    std::vector<Result> lines_regex_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const std::string &regex,
+                                                   bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20)
+    {
+        check_regex(regex, icase);
+        if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) throw Error(ZARC_GPU_E_PARAM, "max_line is 1 to 65536");
+        Search s{&regex, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, true, max_lines, max_line, rec_cap};
+        s.regex = true;
+        std::vector<Result> out = run_frames(archive, archive_len, wanted, false, &s);
+        size_t left = rec_cap;
+        for (Result &r : out) { // the delivery rule over the merged list, as in lines_content_frames
+            if (r.line_records.size() > left) r.line_records.resize(left);
+            left -= r.line_records.size();
+        }
+        return out;
+    }
+
   private:
     struct Search {
         const std::string *pattern; unsigned flags; bool lines = false; uint64_t max_lines = 0, max_line = 0; size_t rec_cap = 0;
+        bool regex = false;                            // `pattern` is a regular expression
         const std::vector<std::string> *set = nullptr; // a set of patterns in place of the one
         std::vector<uint64_t> *hits = nullptr;         // ... and its per-pattern sums over all handles
     };
+    static void check_regex(const std::string &regex, bool icase)
+    {
+        char msg[256];
+        const int rc = zarc_gpu_regex_compile(regex.data(), regex.size(), icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, nullptr, msg, sizeof msg);
+        if (rc != ZARC_GPU_OK) throw Error(rc, msg);
+    }
     static void check_set(const std::vector<std::string> &patterns, bool lines)
     {
         if (patterns.empty() || patterns.size() > ZARC_GPU_SEARCH_MAX_SET) throw Error(ZARC_GPU_E_PARAM, "a set has 1 to 1024 patterns");
@@ -496,7 +531,7 @@ class FrameReader {
         // a set of patterns: one image for all handles, and every handle's own hits
         std::string set_bytes;
         std::vector<uint64_t> set_off, set_len;
-        size_t shortest = search && search->pattern ? search->pattern->size() : 1;
+        size_t shortest = search && search->pattern && !search->regex ? search->pattern->size() : 1;
         if (search && search->set) {
             shortest = SIZE_MAX;
             for (const std::string &p : *search->set) { set_off.push_back(set_bytes.size()); set_len.push_back(p.size()); set_bytes += p; shortest = std::min(shortest, p.size()); }
@@ -540,6 +575,15 @@ class FrameReader {
                     : search && search->set
                         ? zarc_gpu_search_set_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), &pset, search->flags,
                                                     (uint8_t(*)[32])got.data(), status.data(), count.data(), first.data(), which.data(), share_hits[d].data())
+                    : search && search->regex && search->lines
+                        ? zarc_gpu_search_regex_lines_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
+                                                            search->pattern->data(), search->pattern->size(), search->flags, search->max_lines, search->max_line,
+                                                            (uint8_t(*)[32])got.data(), status.data(), count.data(), first.data(), nlines.data(), rec.data(), rec_cap,
+                                                            &rec_used, text.get(), rec_cap * (size_t)search->max_line, &text_used)
+                    : search && search->regex
+                        ? zarc_gpu_search_regex_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
+                                                      search->pattern->data(), search->pattern->size(), search->flags, (uint8_t(*)[32])got.data(),
+                                                      status.data(), count.data(), first.data())
                     : search && search->lines
                         ? zarc_gpu_search_lines_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(),
                                                       search->pattern->data(), search->pattern->size(), search->flags, search->max_lines, search->max_line,
