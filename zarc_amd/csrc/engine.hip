@@ -121,7 +121,7 @@ struct zarc_gpu {
     DevBuf d_set, d_set_hits, d_set_which;      // the compiled set (search_upload_set); hits of every pattern in this part; lowest matching pattern of every frame (decoder order)
     ZarcSetDesc set_desc{};                     // where things lie in d_set
     // a regular expression (zarc_gpu_search_regex_*): zarc_regex_* in place of zarc_search_scan
-    DevBuf d_regex, d_re_summary, d_re_entry;   // the compiled table (search_upload_regex); ZarcRegexSlice and entry state of every slice of this part
+    DevBuf d_regex, d_re_summary, d_re_entry;   // the compiled table (search_prepare); ZarcRegexSlice and entry state of every slice of this part
     // the matching lines of a search (zarc_gpu_search_lines_batch*): zarc_lines_* behind zarc_search_scan, per part
     DevBuf d_ln_slices, d_ln_lines;             // ZarcLineSlice of every slice; matching lines of every frame (decoder order)
     DevBuf d_ln_base, d_ln_deliver;             // what the host decided: first record and number of records of every frame (decoder order)
@@ -650,18 +650,33 @@ struct LinesReq {
     uint8_t *h_text;           // host form: the caller's text buffer (the part's text is gathered into scratch of the handle first)
     LinesRun *run;
 };
-struct SearchReq {
-    const uint8_t *d_pattern;  // device: the pattern, folded when icase
-    uint32_t m, icase;
-    uint64_t *count, *first;   // host, in the caller's order: matching start positions; the lowest, or ZARC_GPU_SEARCH_NONE
-    const LinesReq *ln = nullptr;
-    // a set of patterns in place of the one (zarc_gpu_search_set_*): d_pattern and m are not looked at
-    const ZarcSetDesc *set = nullptr; // the handle's, made by search_upload_set; the blob is h->d_set
-    uint64_t *which = nullptr; // host, in the caller's order: the lowest pattern that matches at first[i], or ZARC_GPU_SEARCH_NONE
-    uint64_t *hits = nullptr;  // host, per pattern, or null: every part ADDS the positions at which the pattern matches in its frames
-    // a regular expression in place of the pattern (zarc_gpu_search_regex_*): d_pattern and m are not looked at
-    const ZarcRegexDfa *d_regex = nullptr; // device: the handle's table, made by search_upload_regex
+// What to search for, as search_prepare has put it on the device: one of three kinds, each with the fields its kernels take
+struct Matcher {
+    enum Kind { PATTERN, SET, REGEX } kind;
+    uint32_t icase;
+    struct Pattern { const uint8_t *d_bytes; uint32_t m; };
+    union {
+        Pattern pattern;              // device: the pattern, folded when icase (zarc_search_scan, zarc_lines_*)
+        const ZarcSetDesc *set;       // the handle's set_desc; the blob is h->d_set, the hits of a part h->d_set_hits (zarc_set_*)
+        const ZarcRegexDfa *d_regex;  // device: the handle's table (zarc_regex_*)
+    };
 };
+struct SearchReq {
+    Matcher match;
+    uint64_t *count, *first;   // host, in the caller's order: matching start positions; the lowest, or ZARC_GPU_SEARCH_NONE
+    uint64_t *which;           // SET; host, in the caller's order: the lowest pattern that matches at first[i], or ZARC_GPU_SEARCH_NONE
+    uint64_t *hits;            // SET; host, per pattern, or null: every part ADDS the positions at which the pattern matches in its frames
+    bool lines;                // gather the matching lines as well, as `ln` says
+    LinesReq ln;
+};
+// the request of the part of a call that starts at the caller's frame a
+SearchReq part_of(SearchReq r, size_t a)
+{
+    r.count += a; r.first += a;
+    if (r.which) r.which += a;
+    if (r.lines) { r.ln.lines += a; r.ln.frame0 += a; }
+    return r;
+}
 int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
 static_assert(sizeof(ZarcLineRec) == sizeof(zarc_gpu_line), "the device's record is the caller's");
 
@@ -1098,6 +1113,251 @@ int zarc_gpu_pack_batch_device_dedup(zarc_gpu_t *h, size_t n, const void *d_src_
 namespace {
 constexpr int UNPACK_SPLIT = -1000; // internal: the decoder's scratch for this batch exceeds the budget, run it in two parts
 
+// ---- the stages behind the decoder: the read-back check of pack, or the search of a verify pass ----
+// What they see of the part unpack_device_once has just decoded.  Every per-frame array, on the host and on the device, is in the decoder's
+// order; the stages queue their work on the engine stream and none of them waits for it but where it says so.
+struct DecodedPart {
+    zarc_gpu *h;
+    size_t n;
+    const std::vector<uint32_t> &order;   // the caller's index of the decoder's frame i
+    const std::vector<uint64_t> &raw_len;
+    const uint8_t *d_base;                // the decoded bytes: frame i at d_base + d_off[i]
+    const uint64_t *d_off;
+    const int32_t *d_status;
+    Timer &t;
+};
+// slice prefix of the part's frames (a slice is ZARC_CHECK_SLICE bytes; every frame has one at least) -> buf; *total: slices in all
+int upload_slices(const DecodedPart &p, DevBuf &buf, const char *too_large, uint64_t *total)
+{
+    zarc_gpu *const h = p.h;
+    std::vector<uint64_t> slices(p.n + 1, 0);
+    for (size_t i = 0; i < p.n; i++) slices[i + 1] = slices[i] + std::max<uint64_t>(1, (p.raw_len[i] + ZARC_CHECK_SLICE - 1) / ZARC_CHECK_SLICE);
+    if (slices[p.n] > 0x7FFFFFFFull) { set_error(h, too_large); return ZARC_GPU_E_PARAM; }
+    *total = slices[p.n];
+    return upload_u64(h, buf, slices.data(), p.n + 1);
+}
+
+// read-back check: decoded bytes against the pack pass's sources (the frame passes are joined; with one group they ran on the engine
+// stream).  Waits for the result.
+int readback_compare(const DecodedPart &p, const PackCheck &chk, const void *d_frames_base)
+{
+    zarc_gpu *const h = p.h;
+    const size_t n = p.n;
+    int rc, e3, e4;
+    uint64_t slices = 0;
+    if ((rc = upload_slices(p, h->d_chk_slices, "read-back check: batch too large", &slices))) return rc;
+    if (chk.entry_map) { // a pass with skipped entries: the frames are a subset of its entries
+        std::vector<uint32_t> mapped(n);
+        for (size_t i = 0; i < n; i++) mapped[i] = chk.entry_map[p.order[i]];
+        if ((rc = upload_u32(h, h->d_chk_order, mapped.data(), n))) return rc;
+    } else if ((rc = upload_u32(h, h->d_chk_order, p.order.data(), n))) return rc;
+    ZHIP(h->d_chk_bad.reserve(n * 4));
+    ZHIP(hipMemsetAsync(h->d_chk_bad.p, 0xFF, n * 4, h->stream));
+    ZHIP(p.t.mark(&e3));
+    hipLaunchKernelGGL(zarc_check_compare, dim3((unsigned)slices), dim3(256), 0, h->stream, (uint32_t)n, h->d_chk_slices.as<uint64_t>(), h->d_chk_order.as<uint32_t>(),
+                       chk.entry0, p.d_base, p.d_off, p.d_status, chk.src_base, h->d_off.as<uint64_t>(),
+                       h->d_len.as<uint64_t>(), (const uint8_t *)d_frames_base, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>(),
+                       chk.trailer ? (chk.xxh ? chk.xxh : h->d_xxh.as<uint64_t>()) : (const uint64_t *)nullptr, h->d_chk_bad.as<uint32_t>());
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&e4));
+    std::vector<uint32_t> bad(n);
+    ZHIP(hipMemcpyAsync(bad.data(), h->d_chk_bad.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+    ZHIP(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; i++) chk.first_bad[p.order[i]] = bad[i];
+    *chk.ms += elapsed(h, e3, e4);
+    return ZARC_GPU_OK;
+}
+
+// what a part's search carries from one of its stages to the next
+struct SearchPart {
+    uint64_t slices = 0;               // of all the part's frames
+    size_t set_lds = 0;                // SET: bytes of the set's image in LDS
+    int e5 = -1, e6 = -1, e7 = -1;     // timer marks: in front of the scan, behind it, behind the first half of the lines
+    float lines_ms2 = 0;               // the second half of the lines
+    std::vector<uint32_t> count, first, which, hits, lines; // what search_collect asked back (decoder order), for search_scatter
+};
+
+// search: the decoded bytes are judged; look through those of the frames that decoded, where they lie
+int search_launch(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
+{
+    zarc_gpu *const h = p.h;
+    const Matcher &mt = srch.match;
+    const uint32_t n = (uint32_t)p.n;
+    int rc;
+    if ((rc = upload_slices(p, h->d_srch_slices, "search: batch too large", &sp.slices))) return rc;
+    const dim3 per_slice((unsigned)sp.slices), per_frame((unsigned)((p.n + 255) / 256)), per_4((unsigned)((p.n + 3) / 4));
+    const uint64_t *const d_slices = h->d_srch_slices.as<uint64_t>(), *const d_raw = h->d_raw_len.as<uint64_t>();
+    ZHIP(h->d_srch_count.reserve(p.n * 4));
+    ZHIP(h->d_srch_first.reserve(p.n * 4));
+    ZHIP(hipMemsetAsync(h->d_srch_count.p, 0, p.n * 4, h->stream));
+    ZHIP(hipMemsetAsync(h->d_srch_first.p, 0xFF, p.n * 4, h->stream));
+    uint32_t *const d_count = h->d_srch_count.as<uint32_t>(), *const d_first = h->d_srch_first.as<uint32_t>();
+    switch (mt.kind) {
+    case Matcher::PATTERN:
+        ZHIP(p.t.mark(&sp.e5));
+        hipLaunchKernelGGL(zarc_search_scan, per_slice, dim3(256), 0, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, mt.pattern.d_bytes, mt.pattern.m,
+                           mt.icase, d_count, d_first);
+        break;
+    case Matcher::SET:
+        sp.set_lds = (size_t)mt.set->lds_words * 4;
+        ZHIP(h->d_set_which.reserve(p.n * 4));
+        if (srch.hits) ZHIP(hipMemsetAsync(h->d_set_hits.p, 0, (size_t)mt.set->count * 4, h->stream)); // (reserved by search_upload_set)
+        ZHIP(p.t.mark(&sp.e5));
+        hipLaunchKernelGGL(zarc_set_scan, per_slice, dim3(256), sp.set_lds, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, *mt.set, h->d_set.as<uint32_t>(),
+                           mt.icase, d_count, d_first, srch.hits ? h->d_set_hits.as<uint32_t>() : (uint32_t *)nullptr);
+        hipLaunchKernelGGL(zarc_set_which, per_frame, dim3(256), 0, h->stream, n, p.d_base, p.d_off, d_raw, *mt.set, h->d_set.as<uint32_t>(), mt.icase,
+                           d_count, d_first, h->d_set_which.as<uint32_t>());
+        break;
+    case Matcher::REGEX: // what every slice does to the state, every slice's entry state from the frame's end down, then the scan
+        ZHIP(h->d_re_summary.reserve(sp.slices * sizeof(ZarcRegexSlice)));
+        ZHIP(h->d_re_entry.reserve(sp.slices));
+        ZHIP(p.t.mark(&sp.e5));
+        hipLaunchKernelGGL(zarc_regex_summary, per_slice, dim3(256), 0, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, mt.d_regex,
+                           h->d_re_summary.as<ZarcRegexSlice>());
+        hipLaunchKernelGGL(zarc_regex_carry, per_4, dim3(256), 0, h->stream, n, d_slices, p.d_status, mt.d_regex, h->d_re_summary.as<ZarcRegexSlice>(),
+                           h->d_re_entry.as<uint8_t>());
+        hipLaunchKernelGGL(zarc_regex_scan, per_slice, dim3(256), 0, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, mt.d_regex,
+                           h->d_re_entry.as<uint8_t>(), d_count, d_first);
+        break;
+    }
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&sp.e6));
+    return ZARC_GPU_OK;
+}
+
+// lines, first half: what every slice holds, what every slice must know of its neighbours, lines[] of every frame
+int lines_mark(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
+{
+    zarc_gpu *const h = p.h;
+    const Matcher &mt = srch.match;
+    const uint32_t n = (uint32_t)p.n;
+    const dim3 per_slice((unsigned)sp.slices);
+    const uint64_t *const d_slices = h->d_srch_slices.as<uint64_t>(), *const d_raw = h->d_raw_len.as<uint64_t>();
+    ZHIP(h->d_ln_slices.reserve(sp.slices * sizeof(ZarcLineSlice)));
+    ZHIP(h->d_ln_lines.reserve(p.n * 4));
+    ZarcLineSlice *const d_ln = h->d_ln_slices.as<ZarcLineSlice>();
+    uint32_t *const d_lines = h->d_ln_lines.as<uint32_t>();
+    switch (mt.kind) {
+    case Matcher::PATTERN:
+        hipLaunchKernelGGL(zarc_lines_mark, per_slice, dim3(256), 0, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, mt.pattern.d_bytes, mt.pattern.m,
+                           mt.icase, d_ln, d_lines);
+        break;
+    case Matcher::SET:
+        hipLaunchKernelGGL(zarc_lines_mark_set, per_slice, dim3(256), sp.set_lds, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, *mt.set,
+                           h->d_set.as<uint32_t>(), mt.icase, d_ln, d_lines);
+        break;
+    case Matcher::REGEX:
+        hipLaunchKernelGGL(zarc_lines_mark_regex, per_slice, dim3(256), 0, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, mt.d_regex,
+                           h->d_re_entry.as<uint8_t>(), d_ln, d_lines);
+        break;
+    }
+    hipLaunchKernelGGL(zarc_lines_carry, dim3((unsigned)((p.n + 3) / 4)), dim3(256), 0, h->stream, n, d_slices, d_raw, d_ln, d_lines);
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&sp.e7));
+    return ZARC_GPU_OK;
+}
+
+// The search's per-frame results are asked back here and are on the host behind the caller's next synchronize -- the one the part's statuses
+// and digests wait for as well -- where search_scatter takes them to the caller's order.
+int search_collect(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
+{
+    zarc_gpu *const h = p.h;
+    const size_t n = p.n;
+    sp.count.resize(n); sp.first.resize(n);
+    ZHIP(hipMemcpyAsync(sp.count.data(), h->d_srch_count.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+    ZHIP(hipMemcpyAsync(sp.first.data(), h->d_srch_first.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (srch.match.kind == Matcher::SET) {
+        sp.which.resize(n);
+        ZHIP(hipMemcpyAsync(sp.which.data(), h->d_set_which.p, n * 4, hipMemcpyDeviceToHost, h->stream));
+        if (srch.hits) { sp.hits.resize(srch.match.set->count); ZHIP(hipMemcpyAsync(sp.hits.data(), h->d_set_hits.p, sp.hits.size() * 4, hipMemcpyDeviceToHost, h->stream)); }
+    }
+    if (srch.lines) { sp.lines.resize(n); ZHIP(hipMemcpyAsync(sp.lines.data(), h->d_ln_lines.p, n * 4, hipMemcpyDeviceToHost, h->stream)); }
+    return ZARC_GPU_OK;
+}
+void search_scatter(const DecodedPart &p, const SearchReq &srch, const SearchPart &sp)
+{
+    auto none = [](uint32_t v) -> uint64_t { return v == 0xFFFFFFFFu ? ZARC_GPU_SEARCH_NONE : v; };
+    for (size_t i = 0; i < p.n; i++) { srch.count[p.order[i]] = sp.count[i]; srch.first[p.order[i]] = none(sp.first[i]); }
+    for (size_t i = 0; i < sp.which.size(); i++) srch.which[p.order[i]] = none(sp.which[i]);
+    for (size_t k = 0; k < sp.hits.size(); k++) srch.hits[k] += sp.hits[k]; // (32-bit per part, 64-bit over the call)
+}
+
+// lines, second half: the delivery rule in the caller's order, then records and text of what this part delivers.  Waits twice: for the
+// records (their text is sized by them) and for the text.
+int lines_deliver(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
+{
+    zarc_gpu *const h = p.h;
+    const Matcher &mt = srch.match;
+    const size_t n = p.n;
+    const LinesReq &ln = srch.ln;
+    LinesRun &run = *ln.run;
+    int rc;
+    std::vector<uint32_t> where(n); // the decoder's index of the caller's frame
+    for (size_t i = 0; i < n; i++) where[p.order[i]] = (uint32_t)i;
+    std::vector<uint64_t> base(n);
+    std::vector<uint32_t> deliver(n);
+    uint64_t nrec = 0;
+    for (size_t c = 0; c < n; c++) {
+        const uint32_t i = where[c];
+        ln.lines[c] = sp.lines[i];
+        uint64_t d = sp.lines[i];
+        if (ln.max_lines && d > ln.max_lines) d = ln.max_lines;
+        d = std::min<uint64_t>(d, ln.rec_cap - run.rec_used - nrec);
+        base[i] = nrec; deliver[i] = (uint32_t)d;
+        nrec += d;
+    }
+    if (!nrec) return ZARC_GPU_OK;
+    if ((rc = upload_u64(h, h->d_ln_base, base.data(), n))) return rc;
+    if ((rc = upload_u32(h, h->d_ln_deliver, deliver.data(), n))) return rc;
+    ZHIP(h->d_ln_rec.reserve(nrec * sizeof(ZarcLineRec)));
+    ZHIP(h->d_ln_total.reserve(8));
+    ZHIP(hipMemsetAsync(h->d_ln_rec.p, 0, nrec * sizeof(ZarcLineRec), h->stream)); // (a record nobody wrote would name no frame and no text)
+    int e8, e9;
+    ZHIP(p.t.mark(&e8));
+    const dim3 per_slice((unsigned)sp.slices);
+    const uint64_t *const d_slices = h->d_srch_slices.as<uint64_t>(), *const d_raw = h->d_raw_len.as<uint64_t>(), *const d_rbase = h->d_ln_base.as<uint64_t>();
+    const ZarcLineSlice *const d_ln = h->d_ln_slices.as<ZarcLineSlice>();
+    const uint32_t *const d_deliver = h->d_ln_deliver.as<uint32_t>();
+    ZarcLineRec *const d_rec = h->d_ln_rec.as<ZarcLineRec>();
+    switch (mt.kind) {
+    case Matcher::PATTERN:
+        hipLaunchKernelGGL(zarc_lines_emit, per_slice, dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, mt.pattern.d_bytes, mt.pattern.m, mt.icase,
+                           d_ln, d_rbase, d_deliver, ln.max_line, d_rec);
+        break;
+    case Matcher::SET:
+        hipLaunchKernelGGL(zarc_lines_emit_set, per_slice, dim3(256), sp.set_lds, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, *mt.set, h->d_set.as<uint32_t>(),
+                           mt.icase, d_ln, d_rbase, d_deliver, ln.max_line, d_rec);
+        break;
+    case Matcher::REGEX:
+        hipLaunchKernelGGL(zarc_lines_emit_regex, per_slice, dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, mt.d_regex, h->d_re_entry.as<uint8_t>(),
+                           d_ln, d_rbase, d_deliver, ln.max_line, d_rec);
+        break;
+    }
+    hipLaunchKernelGGL(zarc_lines_scan, dim3(1), dim3(256), 0, h->stream, nrec, d_rec, h->d_ln_total.as<uint64_t>());
+    ZHIP(hipGetLastError());
+    uint64_t text_bytes = 0;
+    std::vector<ZarcLineRec> recs(nrec);
+    ZHIP(hipMemcpyAsync(recs.data(), h->d_ln_rec.p, nrec * sizeof(ZarcLineRec), hipMemcpyDeviceToHost, h->stream));
+    ZHIP(hipMemcpyAsync(&text_bytes, h->d_ln_total.p, 8, hipMemcpyDeviceToHost, h->stream));
+    ZHIP(hipStreamSynchronize(h->stream));
+    uint8_t *d_text = ln.d_text ? ln.d_text + run.text_used : nullptr;
+    if (!d_text) { ZHIP(h->d_ln_text.reserve(text_bytes + 16)); d_text = h->d_ln_text.as<uint8_t>(); } // (host form: sized by what came of the scan)
+    hipLaunchKernelGGL(zarc_lines_gather, dim3((unsigned)((nrec + 3) / 4)), dim3(256), 0, h->stream, nrec, d_rec, p.d_base, p.d_off, d_text);
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&e9));
+    if (ln.h_text && text_bytes && (rc = lines_text_out(h, ln.h_text + run.text_used, d_text, text_bytes))) return rc;
+    ZHIP(hipStreamSynchronize(h->stream));
+    for (uint64_t k = 0; k < nrec; k++) {
+        zarc_gpu_line &r = ln.rec[run.rec_used + k];
+        memcpy(&r, &recs[k], sizeof r);
+        r.frame = ln.frame0 + p.order[recs[k].frame];
+        r.text_off += run.text_used;
+    }
+    run.rec_used += nrec; run.text_used += text_bytes;
+    sp.lines_ms2 = elapsed(h, e8, e9);
+    return ZARC_GPU_OK;
+}
+
 // own_out: bytes of engine-owned output scratch this call decodes into (verify, read-back check); they count against the budget
 int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off_in, const uint64_t *frame_len_in,
                        void *d_dst_base, const uint64_t *dst_off_in, const uint64_t *raw_len_in, const uint8_t *expect_in, uint8_t *digest,
@@ -1495,35 +1755,8 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     // join: the decode time ends with the last group's frame pass, the whole call with the last hash
     for (int g = 0; g < groups; g++) if (groups > 1) ZHIP(hipStreamWaitEvent(h->stream, h->ev_g[g][5], 0));
     ZHIP(t.mark(&e1));
-    if (chk) {
-        // ---- read-back check: decoded bytes against the pack pass's sources (the frame passes are joined above; with one group they ran
-        // on the engine stream)
-        std::vector<uint64_t> slices(n + 1, 0);
-        for (size_t i = 0; i < n; i++) slices[i + 1] = slices[i] + std::max<uint64_t>(1, (raw_len[i] + ZARC_CHECK_SLICE - 1) / ZARC_CHECK_SLICE);
-        if (slices[n] > 0x7FFFFFFFull) { set_error(h, "read-back check: batch too large"); return ZARC_GPU_E_PARAM; }
-        if ((rc = upload_u64(h, h->d_chk_slices, slices.data(), n + 1))) return rc;
-        if (chk->entry_map) { // a pass with skipped entries: the frames are a subset of its entries
-            std::vector<uint32_t> mapped(n);
-            for (size_t i = 0; i < n; i++) mapped[i] = chk->entry_map[order[i]];
-            if ((rc = upload_u32(h, h->d_chk_order, mapped.data(), n))) return rc;
-        } else if ((rc = upload_u32(h, h->d_chk_order, order.data(), n))) return rc;
-        ZHIP(h->d_chk_bad.reserve(n * 4));
-        ZHIP(hipMemsetAsync(h->d_chk_bad.p, 0xFF, n * 4, h->stream));
-        ZHIP(t.mark(&e3));
-        hipLaunchKernelGGL(zarc_check_compare, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_chk_slices.as<uint64_t>(), h->d_chk_order.as<uint32_t>(),
-                           chk->entry0, (const uint8_t *)d_dst_base, b_dst_off.as<uint64_t>(), h->d_status.as<int32_t>(), chk->src_base, h->d_off.as<uint64_t>(),
-                           h->d_len.as<uint64_t>(), (const uint8_t *)d_frames_base, h->d_dst_off.as<uint64_t>(), h->d_dst_len.as<uint64_t>(),
-                           chk->trailer ? (chk->xxh ? chk->xxh : h->d_xxh.as<uint64_t>()) : (const uint64_t *)nullptr, h->d_chk_bad.as<uint32_t>());
-        ZHIP(hipGetLastError());
-        int e4;
-        ZHIP(t.mark(&e4));
-        std::vector<uint32_t> bad(n);
-        ZHIP(hipMemcpyAsync(bad.data(), h->d_chk_bad.p, n * 4, hipMemcpyDeviceToHost, h->stream));
-        ZHIP(hipStreamSynchronize(h->stream));
-        for (size_t i = 0; i < n; i++) chk->first_bad[order[i]] = bad[i];
-        *chk->ms += elapsed(h, e3, e4);
-        return ZARC_GPU_OK;
-    }
+    const DecodedPart part{h, n, order, raw_len, (const uint8_t *)d_dst_base, b_dst_off.as<uint64_t>(), h->d_status.as<int32_t>(), t};
+    if (chk) return readback_compare(part, *chk, d_frames_base);
     for (int g = 0; g < groups; g++) {
         ZHIP(hipStreamWaitEvent(h->stream, h->ev_g[g][7], 0));
         if (groups > 1) ZHIP(hipStreamWaitEvent(h->stream, h->ev_g[g][9], 0));
@@ -1533,73 +1766,9 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
                        h->d_stored_ck.as<uint32_t>(), h->d_digests.as<uint32_t>(), expect_in ? h->d_expect.as<uint32_t>() : (const uint32_t *)nullptr,
                        h->d_status.as<int32_t>());
     ZHIP(hipGetLastError());
-    int e5 = -1, e6 = -1, e7 = -1;
-    uint64_t slices_total = 0;
-    size_t set_lds = 0; // a set search: bytes of the set's image in LDS
-    float lines_ms2 = 0;
-    if (srch) { // ---- search: the decoded bytes are judged; look through those of the frames that decoded, where they lie
-        std::vector<uint64_t> slices(n + 1, 0);
-        for (size_t i = 0; i < n; i++) slices[i + 1] = slices[i] + std::max<uint64_t>(1, (raw_len[i] + ZARC_CHECK_SLICE - 1) / ZARC_CHECK_SLICE);
-        if (slices[n] > 0x7FFFFFFFull) { set_error(h, "search: batch too large"); return ZARC_GPU_E_PARAM; }
-        if ((rc = upload_u64(h, h->d_srch_slices, slices.data(), n + 1))) return rc;
-        slices_total = slices[n];
-        ZHIP(h->d_srch_count.reserve(n * 4));
-        ZHIP(h->d_srch_first.reserve(n * 4));
-        ZHIP(hipMemsetAsync(h->d_srch_count.p, 0, n * 4, h->stream));
-        ZHIP(hipMemsetAsync(h->d_srch_first.p, 0xFF, n * 4, h->stream));
-        if (srch->set) {
-            set_lds = (size_t)srch->set->lds_words * 4;
-            ZHIP(h->d_set_which.reserve(n * 4));
-            if (srch->hits) ZHIP(hipMemsetAsync(h->d_set_hits.p, 0, (size_t)srch->set->count * 4, h->stream)); // (reserved by search_upload_set)
-        }
-        if (srch->d_regex) {
-            ZHIP(h->d_re_summary.reserve(slices[n] * sizeof(ZarcRegexSlice)));
-            ZHIP(h->d_re_entry.reserve(slices[n]));
-        }
-        ZHIP(t.mark(&e5));
-        if (srch->d_regex) { // what every slice does to the state, every slice's entry state from the frame's end down, then the scan
-            hipLaunchKernelGGL(zarc_regex_summary, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_regex, h->d_re_summary.as<ZarcRegexSlice>());
-            hipLaunchKernelGGL(zarc_regex_carry, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(),
-                               h->d_status.as<int32_t>(), srch->d_regex, h->d_re_summary.as<ZarcRegexSlice>(), h->d_re_entry.as<uint8_t>());
-            hipLaunchKernelGGL(zarc_regex_scan, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_regex, h->d_re_entry.as<uint8_t>(),
-                               h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>());
-        } else if (srch->set) {
-            hipLaunchKernelGGL(zarc_set_scan, dim3((unsigned)slices[n]), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase,
-                               h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>(), srch->hits ? h->d_set_hits.as<uint32_t>() : (uint32_t *)nullptr);
-            hipLaunchKernelGGL(zarc_set_which, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (uint32_t)n, (const uint8_t *)d_dst_base, b_dst_off.as<uint64_t>(),
-                               h->d_raw_len.as<uint64_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase, h->d_srch_count.as<uint32_t>(),
-                               h->d_srch_first.as<uint32_t>(), h->d_set_which.as<uint32_t>());
-        } else {
-            hipLaunchKernelGGL(zarc_search_scan, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_pattern, srch->m, srch->icase,
-                               h->d_srch_count.as<uint32_t>(), h->d_srch_first.as<uint32_t>());
-        }
-        ZHIP(hipGetLastError());
-        ZHIP(t.mark(&e6));
-        if (srch->ln) { // ---- lines, first half: what every slice holds, what every slice must know of its neighbours, lines[] of every frame
-            ZHIP(h->d_ln_slices.reserve(slices[n] * sizeof(ZarcLineSlice)));
-            ZHIP(h->d_ln_lines.reserve(n * 4));
-            if (srch->d_regex)
-                hipLaunchKernelGGL(zarc_lines_mark_regex, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                                   b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_regex, h->d_re_entry.as<uint8_t>(),
-                                   h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
-            else if (srch->set)
-                hipLaunchKernelGGL(zarc_lines_mark_set, dim3((unsigned)slices[n]), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                                   b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase,
-                                   h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
-            else
-            hipLaunchKernelGGL(zarc_lines_mark, dim3((unsigned)slices[n]), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), h->d_status.as<int32_t>(), srch->d_pattern, srch->m, srch->icase,
-                               h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
-            hipLaunchKernelGGL(zarc_lines_carry, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(),
-                               h->d_raw_len.as<uint64_t>(), h->d_ln_slices.as<ZarcLineSlice>(), h->d_ln_lines.as<uint32_t>());
-            ZHIP(hipGetLastError());
-            ZHIP(t.mark(&e7));
-        }
-    }
+    SearchPart sp;
+    if (srch && (rc = search_launch(part, *srch, sp))) return rc;
+    if (srch && srch->lines && (rc = lines_mark(part, *srch, sp))) return rc;
     std::vector<int32_t> st_v;
     std::vector<uint8_t> dg_v;
     int32_t *st = (int32_t *)meta_take(h, n * 4); // results come back through the page-locked arena too, then go to the caller's order
@@ -1608,89 +1777,11 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (!dg) { dg_v.resize(n * 32); dg = dg_v.data(); }
     ZHIP(hipMemcpyAsync(st, h->d_status.p, n * 4, hipMemcpyDeviceToHost, h->stream));
     ZHIP(hipMemcpyAsync(dg, h->d_digests.p, n * 32, hipMemcpyDeviceToHost, h->stream));
-    std::vector<uint32_t> sc, sf;
-    if (srch) {
-        sc.resize(n); sf.resize(n);
-        ZHIP(hipMemcpyAsync(sc.data(), h->d_srch_count.p, n * 4, hipMemcpyDeviceToHost, h->stream));
-        ZHIP(hipMemcpyAsync(sf.data(), h->d_srch_first.p, n * 4, hipMemcpyDeviceToHost, h->stream));
-    }
-    std::vector<uint32_t> sw, sh;
-    if (srch && srch->set) {
-        sw.resize(n);
-        ZHIP(hipMemcpyAsync(sw.data(), h->d_set_which.p, n * 4, hipMemcpyDeviceToHost, h->stream));
-        if (srch->hits) { sh.resize(srch->set->count); ZHIP(hipMemcpyAsync(sh.data(), h->d_set_hits.p, sh.size() * 4, hipMemcpyDeviceToHost, h->stream)); }
-    }
-    std::vector<uint32_t> ln_lines;
-    if (srch && srch->ln) { ln_lines.resize(n); ZHIP(hipMemcpyAsync(ln_lines.data(), h->d_ln_lines.p, n * 4, hipMemcpyDeviceToHost, h->stream)); }
-    ZHIP(hipStreamSynchronize(h->stream));
+    if (srch && (rc = search_collect(part, *srch, sp))) return rc;
+    ZHIP(hipStreamSynchronize(h->stream)); // the one wait of a part for its per-frame results: the verdict's and the search's
     for (size_t i = 0; i < n; i++) { status[order[i]] = st[i]; memcpy(digest + (size_t)order[i] * 32, dg + i * 32, 32); }
-    if (srch) for (size_t i = 0; i < n; i++) { srch->count[order[i]] = sc[i]; srch->first[order[i]] = sf[i] == 0xFFFFFFFFu ? ZARC_GPU_SEARCH_NONE : sf[i]; }
-    if (srch && srch->set) {
-        for (size_t i = 0; i < n; i++) srch->which[order[i]] = sw[i] == 0xFFFFFFFFu ? ZARC_GPU_SEARCH_NONE : sw[i];
-        for (size_t k = 0; k < sh.size(); k++) srch->hits[k] += sh[k]; // (32-bit per part, 64-bit over the call)
-    }
-    if (srch && srch->ln) { // ---- lines, second half: the delivery rule in the caller's order, then records and text of what this part delivers
-        const LinesReq &ln = *srch->ln;
-        LinesRun &run = *ln.run;
-        std::vector<uint32_t> where(n); // the decoder's index of the caller's frame
-        for (size_t i = 0; i < n; i++) where[order[i]] = (uint32_t)i;
-        std::vector<uint64_t> base(n);
-        std::vector<uint32_t> deliver(n);
-        uint64_t nrec = 0;
-        for (size_t c = 0; c < n; c++) {
-            const uint32_t i = where[c];
-            ln.lines[c] = ln_lines[i];
-            uint64_t d = ln_lines[i];
-            if (ln.max_lines && d > ln.max_lines) d = ln.max_lines;
-            d = std::min<uint64_t>(d, ln.rec_cap - run.rec_used - nrec);
-            base[i] = nrec; deliver[i] = (uint32_t)d;
-            nrec += d;
-        }
-        if (nrec) {
-            if ((rc = upload_u64(h, h->d_ln_base, base.data(), n))) return rc;
-            if ((rc = upload_u32(h, h->d_ln_deliver, deliver.data(), n))) return rc;
-            ZHIP(h->d_ln_rec.reserve(nrec * sizeof(ZarcLineRec)));
-            ZHIP(h->d_ln_total.reserve(8));
-            ZHIP(hipMemsetAsync(h->d_ln_rec.p, 0, nrec * sizeof(ZarcLineRec), h->stream)); // (a record nobody wrote would name no frame and no text)
-            int e8, e9;
-            ZHIP(t.mark(&e8));
-            if (srch->d_regex)
-                hipLaunchKernelGGL(zarc_lines_emit_regex, dim3((unsigned)slices_total), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                                   b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), srch->d_regex, h->d_re_entry.as<uint8_t>(), h->d_ln_slices.as<ZarcLineSlice>(),
-                                   h->d_ln_base.as<uint64_t>(), h->d_ln_deliver.as<uint32_t>(), ln.max_line, h->d_ln_rec.as<ZarcLineRec>());
-            else if (srch->set)
-                hipLaunchKernelGGL(zarc_lines_emit_set, dim3((unsigned)slices_total), dim3(256), set_lds, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                                   b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), *srch->set, h->d_set.as<uint32_t>(), srch->icase, h->d_ln_slices.as<ZarcLineSlice>(),
-                                   h->d_ln_base.as<uint64_t>(), h->d_ln_deliver.as<uint32_t>(), ln.max_line, h->d_ln_rec.as<ZarcLineRec>());
-            else
-            hipLaunchKernelGGL(zarc_lines_emit, dim3((unsigned)slices_total), dim3(256), 0, h->stream, (uint32_t)n, h->d_srch_slices.as<uint64_t>(), (const uint8_t *)d_dst_base,
-                               b_dst_off.as<uint64_t>(), h->d_raw_len.as<uint64_t>(), srch->d_pattern, srch->m, srch->icase, h->d_ln_slices.as<ZarcLineSlice>(),
-                               h->d_ln_base.as<uint64_t>(), h->d_ln_deliver.as<uint32_t>(), ln.max_line, h->d_ln_rec.as<ZarcLineRec>());
-            hipLaunchKernelGGL(zarc_lines_scan, dim3(1), dim3(256), 0, h->stream, nrec, h->d_ln_rec.as<ZarcLineRec>(), h->d_ln_total.as<uint64_t>());
-            ZHIP(hipGetLastError());
-            uint64_t text_bytes = 0;
-            std::vector<ZarcLineRec> recs(nrec);
-            ZHIP(hipMemcpyAsync(recs.data(), h->d_ln_rec.p, nrec * sizeof(ZarcLineRec), hipMemcpyDeviceToHost, h->stream));
-            ZHIP(hipMemcpyAsync(&text_bytes, h->d_ln_total.p, 8, hipMemcpyDeviceToHost, h->stream));
-            ZHIP(hipStreamSynchronize(h->stream));
-            uint8_t *d_text = ln.d_text ? ln.d_text + run.text_used : nullptr;
-            if (!d_text) { ZHIP(h->d_ln_text.reserve(text_bytes + 16)); d_text = h->d_ln_text.as<uint8_t>(); } // (host form: sized by what came of the scan)
-            hipLaunchKernelGGL(zarc_lines_gather, dim3((unsigned)((nrec + 3) / 4)), dim3(256), 0, h->stream, nrec, h->d_ln_rec.as<ZarcLineRec>(), (const uint8_t *)d_dst_base,
-                               b_dst_off.as<uint64_t>(), d_text);
-            ZHIP(hipGetLastError());
-            ZHIP(t.mark(&e9));
-            if (ln.h_text && text_bytes && (rc = lines_text_out(h, ln.h_text + run.text_used, d_text, text_bytes))) return rc;
-            ZHIP(hipStreamSynchronize(h->stream));
-            for (uint64_t k = 0; k < nrec; k++) {
-                zarc_gpu_line &r = ln.rec[run.rec_used + k];
-                memcpy(&r, &recs[k], sizeof r);
-                r.frame = ln.frame0 + order[recs[k].frame];
-                r.text_off += run.text_used;
-            }
-            run.rec_used += nrec; run.text_used += text_bytes;
-            lines_ms2 = elapsed(h, e8, e9);
-        }
-    }
+    if (srch) search_scatter(part, *srch, sp);
+    if (srch && srch->lines && (rc = lines_deliver(part, *srch, sp))) return rc;
     if (fastpath && diag_env("ZARC_GPU_DEC_STATS", 0)) { // diagnostics: how many frames had their sequences decoded ahead
         std::vector<uint32_t> fl(n);
         ZHIP(hipMemcpy(fl.data(), h->d_fast.p, n * 4, hipMemcpyDeviceToHost));
@@ -1723,8 +1814,8 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     h->ms[ZARC_GPU_T_XXH64] = t_xxh; // side stream: overlaps the digest pass
     h->ms[ZARC_GPU_T_BLAKE3] = t_b3;
     h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e3);
-    if (srch) { h->ms[ZARC_GPU_T_SEARCH] = elapsed(h, e5, e6); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e6); }
-    if (srch && srch->ln) { h->ms[ZARC_GPU_T_LINES] = elapsed(h, e6, e7) + lines_ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e7) + lines_ms2; }
+    if (srch) { h->ms[ZARC_GPU_T_SEARCH] = elapsed(h, sp.e5, sp.e6); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, sp.e6); }
+    if (srch && srch->lines) { h->ms[ZARC_GPU_T_LINES] = elapsed(h, sp.e6, sp.e7) + sp.lines_ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, sp.e7) + sp.lines_ms2; }
     return ZARC_GPU_OK;
 }
 
@@ -1774,10 +1865,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
         const size_t a = part[p], m = part[p + 1] - a;
         PackCheck sub{};
         if (chk) { sub = *chk; sub.first_bad += a; if (chk->entry_map) sub.entry_map += a; else sub.entry0 += (uint32_t)a; }
-        SearchReq ssub{};
-        LinesReq lsub{};
-        if (srch) { ssub = *srch; ssub.count += a; ssub.first += a; if (srch->which) ssub.which += a; }
-        if (srch && srch->ln) { lsub = *srch->ln; lsub.lines += a; lsub.frame0 += a; ssub.ln = &lsub; }
+        const SearchReq ssub = srch ? part_of(*srch, a) : SearchReq{};
         rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
                                  digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr);
         if (rc) return rc;
@@ -1813,114 +1901,18 @@ int zarc_gpu_verify_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_b
 
 } // extern "C"
 namespace {
-// the arguments every search entry point checks the same way, before anything else is looked at
-int search_check_args(zarc_gpu_t *h, const void *pattern, size_t pattern_len, unsigned flags, const void *digest, const int *status, const uint64_t *count,
-                      const uint64_t *first)
+// Frames of 4 GiB and more are refused before any size arithmetic or staging.  frame (host forms): every frame with bytes has an address.
+template <typename Len> // (uint64_t in the device forms, size_t in the host forms)
+int check_frame_sizes(zarc_gpu_t *h, size_t n, const Len *frame_len, const Len *raw_len, const void *const *frame = nullptr)
 {
-    if (!h) return ZARC_GPU_E_PARAM;
-    if (!pattern || pattern_len == 0 || pattern_len > ZARC_GPU_SEARCH_MAX_PATTERN) { set_error(h, "search: the pattern has 1 to 256 bytes"); return ZARC_GPU_E_PARAM; }
-    if (flags & ~(unsigned)ZARC_GPU_SEARCH_ICASE) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
-    if (!digest || !status || !count || !first) return ZARC_GPU_E_PARAM;
-    return 0;
-}
-// the pattern goes up once per call, folded here when the text is folded there ('A'..'Z' only)
-int search_upload_pattern(zarc_gpu_t *h, const void *pattern, size_t pattern_len, unsigned flags)
-{
-    uint8_t pat[ZARC_GPU_SEARCH_MAX_PATTERN] = {0};
-    memcpy(pat, pattern, pattern_len);
-    if (flags & ZARC_GPU_SEARCH_ICASE) for (size_t k = 0; k < pattern_len; k++) if (pat[k] >= 'A' && pat[k] <= 'Z') pat[k] |= 0x20;
-    ZHIP(h->d_srch_pat.reserve(sizeof pat));
-    ZHIP(hipMemcpy(h->d_srch_pat.p, pat, sizeof pat, hipMemcpyHostToDevice));
-    return 0;
-}
-} // namespace
-extern "C" {
-
-// zarc_gpu_verify_batch_device with zarc_search_scan behind the verdict of every part
-int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
-                                 const uint64_t *raw_len, const uint8_t *expect, const void *pattern, size_t pattern_len, unsigned flags,
-                                 uint8_t *digest, int *status, uint64_t *count, uint64_t *first)
-{
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if ((rc = search_check_args(h, pattern, pattern_len, flags, digest, status, count, first))) return rc;
-    if (n == 0) return ZARC_GPU_OK;
-    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
-    for (size_t i = 0; i < n; i++)
-        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
-    if (!h->nested && (rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc; // (the host form has done it for all its chunks)
-    const SearchReq srch{h->d_srch_pat.as<uint8_t>(), (uint32_t)pattern_len, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
-    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
-}
-} // extern "C"
-namespace {
-// what the lines entry points check on top of search_check_args; -> 0, ZARC_GPU_E_PARAM or ZARC_GPU_E_DSTSIZE
-int lines_check_args(zarc_gpu_t *h, const void *pattern, size_t pattern_len, uint64_t max_line, const uint64_t *lines, const zarc_gpu_line *rec, size_t rec_cap,
-                     const size_t *rec_used, const void *text, size_t text_cap, const size_t *text_used)
-{
-    if (!lines || !rec_used || !text_used) return ZARC_GPU_E_PARAM;
-    if (rec_cap && (!rec || !text)) return ZARC_GPU_E_PARAM;
-    if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) { set_error(h, "search_lines: max_line is 1 to 65536"); return ZARC_GPU_E_PARAM; }
-    if (memchr(pattern, 0x0A, pattern_len)) { set_error(h, "search_lines: the pattern must not contain a newline"); return ZARC_GPU_E_PARAM; }
-    if (rec_cap > SIZE_MAX / (size_t)max_line || text_cap < rec_cap * (size_t)max_line) { set_error(h, "search_lines: text_cap is below rec_cap * max_line"); return ZARC_GPU_E_DSTSIZE; }
-    return 0;
-}
-// one part of a lines call (the whole of the device form, a chunk of the host form): search's pass with the line kernels behind it
-int search_lines_part(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, const uint64_t *raw_len,
-                      const uint8_t *expect, size_t pattern_len, unsigned flags, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, const LinesReq &ln,
-                      uint64_t *which = nullptr, uint64_t *hits = nullptr, bool regex = false) // which: the handle's set (search_upload_set) in place of its pattern; regex: its table (search_upload_regex)
-{
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    SearchReq srch{h->d_srch_pat.as<uint8_t>(), (uint32_t)pattern_len, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
-    srch.ln = &ln;
-    if (which) { srch.set = &h->set_desc; srch.which = which; srch.hits = hits; }
-    if (regex) srch.d_regex = h->d_regex.as<ZarcRegexDfa>();
-    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
-}
-} // namespace
-extern "C" {
-
-// zarc_gpu_search_batch_device with zarc_lines_* behind the search kernel of every part
-int zarc_gpu_search_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
-                                       const uint64_t *raw_len, const uint8_t *expect, const void *pattern, size_t pattern_len, unsigned flags,
-                                       uint64_t max_lines, uint64_t max_line, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, uint64_t *lines,
-                                       zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *d_text, size_t text_cap, size_t *text_used)
-{
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if ((rc = search_check_args(h, pattern, pattern_len, flags, digest, status, count, first))) return rc;
-    if ((rc = lines_check_args(h, pattern, pattern_len, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used))) return rc;
-    *rec_used = 0; *text_used = 0;
-    if (n == 0) return ZARC_GPU_OK;
-    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
-    for (size_t i = 0; i < n; i++)
-        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
-    if ((rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc;
-    LinesRun run;
-    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, (uint8_t *)d_text, nullptr, &run};
-    rc = search_lines_part(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, pattern_len, flags, digest, status, count, first, ln);
-    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
-    return rc;
-}
-
-} // extern "C"
-namespace {
-// what every set entry point checks the same way, before anything else is looked at (search_check_args for a set); lines: no 0x0A either
-int search_set_check_args(zarc_gpu_t *h, const zarc_gpu_pattern_set *set, unsigned flags, bool lines, const void *digest, const int *status, const uint64_t *count,
-                          const uint64_t *first, const uint64_t *which)
-{
-    if (!h) return ZARC_GPU_E_PARAM;
-    if (!set || !set->bytes || !set->off || !set->len) { set_error(h, "search_set: a set and its members are needed"); return ZARC_GPU_E_PARAM; }
-    if (set->count == 0 || set->count > ZARC_GPU_SEARCH_MAX_SET) { set_error(h, "search_set: a set has 1 to 1024 patterns"); return ZARC_GPU_E_PARAM; }
-    for (size_t k = 0; k < set->count; k++) {
-        if (set->len[k] == 0 || set->len[k] > ZARC_GPU_SEARCH_MAX_PATTERN) { set_error(h, "search_set: a pattern has 1 to 256 bytes"); return ZARC_GPU_E_PARAM; }
-        if (lines && memchr((const uint8_t *)set->bytes + set->off[k], 0x0A, set->len[k])) { set_error(h, "search_set_lines: a pattern must not contain a newline"); return ZARC_GPU_E_PARAM; }
+    for (size_t i = 0; i < n; i++) {
+        if (frame && frame_len[i] && !frame[i]) return ZARC_GPU_E_PARAM;
+        if ((uint64_t)frame_len[i] >= 0xFFFFFFF0ull || (uint64_t)raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
     }
-    if (flags & ~(unsigned)ZARC_GPU_SEARCH_ICASE) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
-    if (!digest || !status || !count || !first || !which) return ZARC_GPU_E_PARAM;
     return 0;
 }
+
+// ---- search (zarc_gpu_search_*): a verify pass that looks through what it decoded, per part, while that part's bytes are in d_vout ----
 uint32_t ceil_log2(uint32_t v) { uint32_t l = 0; while ((1u << l) < v) l++; return l; }
 // The set goes up once per call, compiled into what zdec_search_set.hip reads (the layout is described there and at ZarcSetDesc) and folded
 // here when the text is folded there.  Filters and tables are sized from the number of distinct keys of each length class.
@@ -1981,129 +1973,169 @@ int search_upload_set(zarc_gpu_t *h, const zarc_gpu_pattern_set *set, unsigned f
     h->set_desc = sd;
     return 0;
 }
+static_assert(sizeof(ZarcRegexDfa) == sizeof(zarc_gpu_regex_dfa) && offsetof(ZarcRegexDfa, delta) == offsetof(zarc_gpu_regex_dfa, delta), "the device's table is the caller's");
+
+// What the twelve entry points are called with, beside the frames: what to search for, where the results go, and (lines) what to gather
+struct MatcherArgs {
+    Matcher::Kind kind;
+    const void *text;                 // PATTERN: its bytes; REGEX: the expression
+    size_t text_len;
+    const zarc_gpu_pattern_set *set;  // SET
+    unsigned flags;
+};
+struct SearchOut { uint8_t *digest; int *status; uint64_t *count, *first, *which /* SET */, *hits /* SET, or null */; };
+struct LinesArgs {
+    uint64_t max_lines, max_line;
+    uint64_t *lines;
+    zarc_gpu_line *rec;
+    size_t rec_cap, *rec_used;
+    void *text;                       // device form: on the device; host form: the caller's memory
+    size_t text_cap, *text_used;
+};
+
+// Every check of a search call that does not look at the frames, in the order the callers are promised (the matcher, the flags, the result
+// arrays, then the lines arguments), the zeroing of what the call adds to, the call's request, and -- unless the call is empty -- the matcher's
+// way to the device: once per call, whatever the call is cut into.  A bad expression is refused whatever n is.
+// host_text: the lines' text goes to the caller's memory (host form), not to the device
+int search_prepare(zarc_gpu_t *h, size_t n, const MatcherArgs &a, const SearchOut &out, const LinesArgs *la, bool host_text, LinesRun *run, SearchReq *req)
+{
+    const unsigned unknown = a.flags & ~(unsigned)ZARC_GPU_SEARCH_ICASE;
+    const bool no_out = !out.digest || !out.status || !out.count || !out.first;
+    zarc_gpu_regex_dfa dfa; // REGEX: compiled by the checks, uploaded below
+    switch (a.kind) {
+    case Matcher::PATTERN:
+        if (!a.text || a.text_len == 0 || a.text_len > ZARC_GPU_SEARCH_MAX_PATTERN) { set_error(h, "search: the pattern has 1 to 256 bytes"); return ZARC_GPU_E_PARAM; }
+        if (unknown) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
+        if (no_out) return ZARC_GPU_E_PARAM;
+        break;
+    case Matcher::SET:
+        if (!a.set || !a.set->bytes || !a.set->off || !a.set->len) { set_error(h, "search_set: a set and its members are needed"); return ZARC_GPU_E_PARAM; }
+        if (a.set->count == 0 || a.set->count > ZARC_GPU_SEARCH_MAX_SET) { set_error(h, "search_set: a set has 1 to 1024 patterns"); return ZARC_GPU_E_PARAM; }
+        for (size_t k = 0; k < a.set->count; k++) {
+            if (a.set->len[k] == 0 || a.set->len[k] > ZARC_GPU_SEARCH_MAX_PATTERN) { set_error(h, "search_set: a pattern has 1 to 256 bytes"); return ZARC_GPU_E_PARAM; }
+            if (la && memchr((const uint8_t *)a.set->bytes + a.set->off[k], 0x0A, a.set->len[k])) { set_error(h, "search_set_lines: a pattern must not contain a newline"); return ZARC_GPU_E_PARAM; }
+        }
+        if (unknown) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
+        if (no_out || !out.which) return ZARC_GPU_E_PARAM;
+        break;
+    case Matcher::REGEX: {
+        if (unknown) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
+        std::string err;
+        const int rc = zre::compile(a.text, a.text_len, a.flags, &dfa, err);
+        if (rc) { set_error(h, err.c_str()); return rc; }
+        if (no_out) return ZARC_GPU_E_PARAM;
+        break; }
+    }
+    if (la) { // -> ZARC_GPU_E_PARAM or ZARC_GPU_E_DSTSIZE
+        if (!la->lines || !la->rec_used || !la->text_used) return ZARC_GPU_E_PARAM;
+        if (la->rec_cap && (!la->rec || !la->text)) return ZARC_GPU_E_PARAM;
+        if (la->max_line < 1 || la->max_line > ZARC_GPU_LINES_MAX_LINE) { set_error(h, "search_lines: max_line is 1 to 65536"); return ZARC_GPU_E_PARAM; }
+        if (a.kind == Matcher::PATTERN && memchr(a.text, 0x0A, a.text_len)) { set_error(h, "search_lines: the pattern must not contain a newline"); return ZARC_GPU_E_PARAM; }
+        if (la->rec_cap > SIZE_MAX / (size_t)la->max_line || la->text_cap < la->rec_cap * (size_t)la->max_line) { set_error(h, "search_lines: text_cap is below rec_cap * max_line"); return ZARC_GPU_E_DSTSIZE; }
+        *la->rec_used = 0; *la->text_used = 0;
+    }
+    if (a.kind == Matcher::SET && out.hits) memset(out.hits, 0, a.set->count * sizeof *out.hits); // (every part adds to them)
+    *req = SearchReq{Matcher{a.kind, a.flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, {}}, out.count, out.first, out.which, out.hits, la != nullptr, LinesReq{}};
+    if (la) req->ln = LinesReq{la->max_lines, (uint32_t)la->max_line, la->lines, 0, la->rec, la->rec_cap, host_text ? nullptr : (uint8_t *)la->text,
+                               host_text ? (uint8_t *)la->text : nullptr, run};
+    if (n == 0) return 0;
+    switch (a.kind) {
+    case Matcher::PATTERN: { // folded here when the text is folded there ('A'..'Z' only)
+        uint8_t pat[ZARC_GPU_SEARCH_MAX_PATTERN] = {0};
+        memcpy(pat, a.text, a.text_len);
+        if (req->match.icase) for (size_t k = 0; k < a.text_len; k++) if (pat[k] >= 'A' && pat[k] <= 'Z') pat[k] |= 0x20;
+        ZHIP(h->d_srch_pat.reserve(sizeof pat));
+        ZHIP(hipMemcpy(h->d_srch_pat.p, pat, sizeof pat, hipMemcpyHostToDevice));
+        req->match.pattern = Matcher::Pattern{h->d_srch_pat.as<uint8_t>(), (uint32_t)a.text_len};
+        return 0; }
+    case Matcher::SET:
+        req->match.set = &h->set_desc;
+        return search_upload_set(h, a.set, a.flags);
+    case Matcher::REGEX:
+        ZHIP(h->d_regex.reserve(sizeof dfa));
+        ZHIP(hipMemcpy(h->d_regex.p, &dfa, sizeof dfa, hipMemcpyHostToDevice));
+        req->match.d_regex = h->d_regex.as<ZarcRegexDfa>();
+        return 0;
+    }
+    return 0;
+}
+
+// The six device forms: zarc_gpu_verify_batch_device with the matcher's kernels behind the verdict of every part (and the line kernels
+// behind those)
+int search_call_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, const uint64_t *raw_len,
+                       const uint8_t *expect, const MatcherArgs &a, const LinesArgs *la, const SearchOut &out)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    SearchReq req;
+    LinesRun run;
+    if ((rc = search_prepare(h, n, a, out, la, /*host_text=*/false, &run, &req))) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
+    if ((rc = check_frame_sizes(h, n, frame_len, raw_len))) return rc;
+    rc = unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, out.digest, out.status, nullptr, &req);
+    if (la) { *la->rec_used = run.rec_used; *la->text_used = (size_t)run.text_used; }
+    return rc;
+}
 } // namespace
 extern "C" {
 
-// zarc_gpu_search_batch_device with zarc_set_scan and zarc_set_which in place of zarc_search_scan
+int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                 const uint64_t *raw_len, const uint8_t *expect, const void *pattern, size_t pattern_len, unsigned flags,
+                                 uint8_t *digest, int *status, uint64_t *count, uint64_t *first)
+{
+    return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, MatcherArgs{Matcher::PATTERN, pattern, pattern_len, nullptr, flags}, nullptr,
+                              SearchOut{digest, status, count, first, nullptr, nullptr});
+}
+int zarc_gpu_search_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                       const uint64_t *raw_len, const uint8_t *expect, const void *pattern, size_t pattern_len, unsigned flags,
+                                       uint64_t max_lines, uint64_t max_line, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, uint64_t *lines,
+                                       zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *d_text, size_t text_cap, size_t *text_used)
+{
+    const LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used};
+    return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, MatcherArgs{Matcher::PATTERN, pattern, pattern_len, nullptr, flags}, &la,
+                              SearchOut{digest, status, count, first, nullptr, nullptr});
+}
 int zarc_gpu_search_set_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                                      const uint64_t *raw_len, const uint8_t *expect, const zarc_gpu_pattern_set *set, unsigned flags,
                                      uint8_t *digest, int *status, uint64_t *count, uint64_t *first, uint64_t *which, uint64_t *hits)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if ((rc = search_set_check_args(h, set, flags, false, digest, status, count, first, which))) return rc;
-    if (hits && !h->nested) memset(hits, 0, set->count * sizeof *hits); // (the host form has done it for all its chunks)
-    if (n == 0) return ZARC_GPU_OK;
-    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
-    for (size_t i = 0; i < n; i++)
-        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
-    if (!h->nested && (rc = search_upload_set(h, set, flags))) return rc;
-    SearchReq srch{nullptr, 0, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
-    srch.set = &h->set_desc; srch.which = which; srch.hits = hits;
-    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
+    return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, MatcherArgs{Matcher::SET, nullptr, 0, set, flags}, nullptr,
+                              SearchOut{digest, status, count, first, which, hits});
 }
-
-// zarc_gpu_search_lines_batch_device with the set's kernels in place of the pattern's
 int zarc_gpu_search_set_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                                            const uint64_t *raw_len, const uint8_t *expect, const zarc_gpu_pattern_set *set, unsigned flags,
                                            uint64_t max_lines, uint64_t max_line, uint8_t *digest, int *status, uint64_t *count, uint64_t *first,
                                            uint64_t *which, uint64_t *hits, uint64_t *lines, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used,
                                            void *d_text, size_t text_cap, size_t *text_used)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if ((rc = search_set_check_args(h, set, flags, true, digest, status, count, first, which))) return rc;
-    if ((rc = lines_check_args(h, "", 0, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used))) return rc;
-    *rec_used = 0; *text_used = 0;
-    if (hits) memset(hits, 0, set->count * sizeof *hits);
-    if (n == 0) return ZARC_GPU_OK;
-    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
-    for (size_t i = 0; i < n; i++)
-        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
-    if ((rc = search_upload_set(h, set, flags))) return rc;
-    LinesRun run;
-    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, (uint8_t *)d_text, nullptr, &run};
-    rc = search_lines_part(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, 0, flags, digest, status, count, first, ln, which, hits);
-    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
-    return rc;
+    const LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used};
+    return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, MatcherArgs{Matcher::SET, nullptr, 0, set, flags}, &la,
+                              SearchOut{digest, status, count, first, which, hits});
 }
-} // extern "C"
-namespace {
-static_assert(sizeof(ZarcRegexDfa) == sizeof(zarc_gpu_regex_dfa) && offsetof(ZarcRegexDfa, delta) == offsetof(zarc_gpu_regex_dfa, delta), "the device's table is the caller's");
-// what every regex entry point checks the same way, before anything else is looked at (search_check_args for an expression), and the
-// table: compiled here, once per call -- a bad expression is refused whatever n is
-int search_regex_check_args(zarc_gpu_t *h, const void *regex, size_t regex_len, unsigned flags, const void *digest, const int *status, const uint64_t *count,
-                            const uint64_t *first, zarc_gpu_regex_dfa *dfa)
-{
-    if (!h) return ZARC_GPU_E_PARAM;
-    if (flags & ~(unsigned)ZARC_GPU_SEARCH_ICASE) { set_error(h, "search: unknown flag"); return ZARC_GPU_E_PARAM; }
-    std::string err;
-    const int rc = zre::compile(regex, regex_len, flags, dfa, err);
-    if (rc) { set_error(h, err.c_str()); return rc; }
-    if (!digest || !status || !count || !first) return ZARC_GPU_E_PARAM;
-    return 0;
-}
-int search_upload_regex(zarc_gpu_t *h, const zarc_gpu_regex_dfa *dfa)
-{
-    ZHIP(h->d_regex.reserve(sizeof *dfa));
-    ZHIP(hipMemcpy(h->d_regex.p, dfa, sizeof *dfa, hipMemcpyHostToDevice));
-    return 0;
-}
-} // namespace
-extern "C" {
-
-int zarc_gpu_regex_compile(const void *regex, size_t regex_len, unsigned flags, zarc_gpu_regex_dfa *out, char *err, size_t err_cap)
-{
-    std::string msg;
-    const int rc = zre::compile(regex, regex_len, flags, out, msg);
-    if (err && err_cap) { const size_t k = std::min(msg.size(), err_cap - 1); memcpy(err, msg.data(), k); err[k] = 0; }
-    return rc;
-}
-
-// zarc_gpu_search_batch_device with zarc_regex_summary, zarc_regex_carry and zarc_regex_scan in place of zarc_search_scan
 int zarc_gpu_search_regex_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                                        const uint64_t *raw_len, const uint8_t *expect, const void *regex, size_t regex_len, unsigned flags,
                                        uint8_t *digest, int *status, uint64_t *count, uint64_t *first)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if (!h->nested) { // (the host form has compiled and uploaded the table for all its chunks)
-        zarc_gpu_regex_dfa dfa;
-        if ((rc = search_regex_check_args(h, regex, regex_len, flags, digest, status, count, first, &dfa))) return rc;
-        if (n == 0) return ZARC_GPU_OK;
-        if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
-        for (size_t i = 0; i < n; i++)
-            if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
-        if ((rc = search_upload_regex(h, &dfa))) return rc;
-    }
-    if (n == 0) return ZARC_GPU_OK;
-    SearchReq srch{nullptr, 0, flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, count, first};
-    srch.d_regex = h->d_regex.as<ZarcRegexDfa>();
-    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, &srch);
+    return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, MatcherArgs{Matcher::REGEX, regex, regex_len, nullptr, flags}, nullptr,
+                              SearchOut{digest, status, count, first, nullptr, nullptr});
 }
-
-// zarc_gpu_search_lines_batch_device with the automaton's kernels in place of the pattern's
 int zarc_gpu_search_regex_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                                              const uint64_t *raw_len, const uint8_t *expect, const void *regex, size_t regex_len, unsigned flags,
                                              uint64_t max_lines, uint64_t max_line, uint8_t *digest, int *status, uint64_t *count, uint64_t *first,
                                              uint64_t *lines, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *d_text, size_t text_cap,
                                              size_t *text_used)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    zarc_gpu_regex_dfa dfa;
-    if ((rc = search_regex_check_args(h, regex, regex_len, flags, digest, status, count, first, &dfa))) return rc;
-    if ((rc = lines_check_args(h, "", 0, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used))) return rc;
-    *rec_used = 0; *text_used = 0;
-    if (n == 0) return ZARC_GPU_OK;
-    if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
-    for (size_t i = 0; i < n; i++)
-        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
-    if ((rc = search_upload_regex(h, &dfa))) return rc;
-    LinesRun run;
-    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, (uint8_t *)d_text, nullptr, &run};
-    rc = search_lines_part(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, 0, flags, digest, status, count, first, ln, nullptr, nullptr, true);
-    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
+    const LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used};
+    return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, MatcherArgs{Matcher::REGEX, regex, regex_len, nullptr, flags}, &la,
+                              SearchOut{digest, status, count, first, nullptr, nullptr});
+}
+
+int zarc_gpu_regex_compile(const void *regex, size_t regex_len, unsigned flags, zarc_gpu_regex_dfa *out, char *err, size_t err_cap)
+{
+    std::string msg;
+    const int rc = zre::compile(regex, regex_len, flags, out, msg);
+    if (err && err_cap) { const size_t k = std::min(msg.size(), err_cap - 1); memcpy(err, msg.data(), k); err[k] = 0; }
     return rc;
 }
 
@@ -2221,8 +2253,7 @@ int zarc_gpu_repack_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_b
     if (rc) return rc;
     if (n == 0) return ZARC_GPU_OK;
     if (!d_frames_base || !frame_off || !frame_len || !raw_len || !d_dst || !dst_off || !dst_len || !digest || !status) return ZARC_GPU_E_PARAM;
-    for (size_t i = 0; i < n; i++)
-        if (frame_len[i] >= 0xFFFFFFF0ull || raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; } // before any size arithmetic
+    if ((rc = check_frame_sizes(h, n, frame_len, raw_len))) return rc;
     uint64_t need = 0;
     for (size_t i = 0; i < n; i++) need += zarc_gpu_bound((size_t)raw_len[i]);
     if (need > dst_cap) return ZARC_GPU_E_DSTSIZE;
@@ -2637,22 +2668,19 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 // The chunk loop of zarc_gpu_unpack_batch without its outbound half: chunk c+1's frames come in while chunk c is decoded and judged;
 // nothing but statuses and digests goes back.  A chunk's decoded bytes live in the handle's scratch (unpack_device_split), so the
 // chunks are cut by the same weight as unpack's.
-// With a pattern (zarc_gpu_search_batch) every chunk is searched as well, and two more words per frame go back; with a set of them
-// (zarc_gpu_search_set_batch) three, and every chunk adds to the call's hits.
+// With a search request every chunk is searched as well (the matcher is on the device already: search_prepare), its results go back too,
+// and a set's chunks add to the call's hits.
 } // extern "C"
 namespace {
 int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
-                     const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const void *pattern,
-                     size_t pattern_len, unsigned flags, uint64_t *count, uint64_t *first, const LinesReq *ln = nullptr,
-                     const zarc_gpu_pattern_set *set = nullptr, uint64_t *which = nullptr, uint64_t *hits = nullptr, bool regex = false)
+                     const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const SearchReq *srch)
 {
     int rc = 0;
     if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
     NestedCall nested(h);
+    if ((rc = check_frame_sizes(h, n, frame_len, raw_len, frame))) return rc;
     std::vector<uint64_t> in_sz(n), out_sz(n), weight(n), flen(n), rlen(n);
     for (size_t i = 0; i < n; i++) {
-        if (frame_len[i] && !frame[i]) return ZARC_GPU_E_PARAM;
-        if ((uint64_t)frame_len[i] >= 0xFFFFFFF0ull || (uint64_t)raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; } // before any size arithmetic or staging
         flen[i] = frame_len[i]; rlen[i] = raw_len[i];
         in_sz[i] = align_up(frame_len[i], ZARC_GPU_ALIGN);
         out_sz[i] = align_up(raw_len[i], ZARC_GPU_ALIGN);
@@ -2688,26 +2716,12 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
         std::vector<uint64_t> foff(m);
         uint64_t fa = 0;
         for (size_t k = 0; k < m; k++) { foff[k] = fa; fa += in_sz[i0 + k]; }
-        if (ln) { // (the chunks are ranges of the caller's frames in the caller's order: the running remainder of rec_cap goes from one to the next)
-            LinesReq sub = *ln;
-            sub.lines += i0; sub.frame0 += i0;
-            rc = search_lines_part(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0, expect ? (const uint8_t *)expect[i0] : nullptr,
-                                   pattern_len, flags, (uint8_t *)digest[i0], status + i0, count + i0, first + i0, sub, set ? which + i0 : nullptr, hits, regex);
-        } else if (regex) // (pattern, pattern_len: the expression; the nested call does not look at it, the handle's table is up)
-            rc = zarc_gpu_search_regex_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
-                                                    expect ? (const uint8_t *)expect[i0] : nullptr, pattern, pattern_len, flags, (uint8_t *)digest[i0], status + i0,
-                                                    count + i0, first + i0);
-        else if (set)
-            rc = zarc_gpu_search_set_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
-                                                  expect ? (const uint8_t *)expect[i0] : nullptr, set, flags, (uint8_t *)digest[i0], status + i0,
-                                                  count + i0, first + i0, which + i0, hits);
-        else if (pattern)
-            rc = zarc_gpu_search_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
-                                              expect ? (const uint8_t *)expect[i0] : nullptr, pattern, pattern_len, flags, (uint8_t *)digest[i0], status + i0,
-                                              count + i0, first + i0);
-        else
-            rc = zarc_gpu_verify_batch_device(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, rlen.data() + i0,
-                                              expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0);
+        // every chunk is a batch call of its own to the clocks and the descriptor arena; the copy counters are the whole call's (NestedCall).
+        // The chunks are ranges of the caller's frames in the caller's order: the running remainder of rec_cap goes from one to the next
+        const SearchReq sub = srch ? part_of(*srch, i0) : SearchReq{};
+        if (!(rc = check_common(h, m)))
+            rc = unpack_device_split(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, nullptr, nullptr, rlen.data() + i0,
+                                     expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0, nullptr, srch ? &sub : nullptr);
         if (helper.joinable()) helper.join();
         if (rc) return rc;
         if (helper_rc) return helper_rc;
@@ -2715,6 +2729,22 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
     }
     for (int t = 0; t < ZARC_GPU_T_COUNT; t++) h->ms[t] = sum[t];
     return ZARC_GPU_OK;
+}
+
+// The six host forms: verify's chunk loop with the search behind every chunk's verdict.  The compressed bytes go up; 52 bytes per frame come
+// back (a set: 60, and the hits), and with lines the matching lines' bytes.
+int search_call_host(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len, const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN],
+                     const MatcherArgs &a, const LinesArgs *la, const SearchOut &out)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    SearchReq req;
+    LinesRun run;
+    if ((rc = search_prepare(h, n, a, out, la, /*host_text=*/true, &run, &req))) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, (uint8_t (*)[ZARC_GPU_DIGEST_LEN])out.digest, out.status, &req);
+    if (la) { *la->rec_used = run.rec_used; *la->text_used = (size_t)run.text_used; }
+    return rc;
 }
 } // namespace
 extern "C" {
@@ -2725,109 +2755,57 @@ int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
     int rc = check_common(h, n);
     if (rc) return rc;
     if (n == 0) return ZARC_GPU_OK;
-    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, 0, 0, nullptr, nullptr);
+    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr);
 }
-
-// verify's chunk loop with the search behind every chunk's verdict: the compressed bytes go up, 52 bytes per frame come back
 int zarc_gpu_search_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                           const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *pattern, size_t pattern_len, unsigned flags,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if ((rc = search_check_args(h, pattern, pattern_len, flags, digest, status, count, first))) return rc;
-    if (n == 0) return ZARC_GPU_OK;
-    if ((rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc;
-    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, pattern, pattern_len, flags, count, first);
+    return search_call_host(h, n, frame, frame_len, raw_len, expect, MatcherArgs{Matcher::PATTERN, pattern, pattern_len, nullptr, flags}, nullptr,
+                            SearchOut{(uint8_t *)digest, status, count, first, nullptr, nullptr});
 }
-// search's chunk loop with the line kernels behind every chunk's search: the compressed bytes go up, the matching lines' bytes come back
 int zarc_gpu_search_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                                 const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *pattern, size_t pattern_len, unsigned flags, uint64_t max_lines,
                                 uint64_t max_line, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *lines,
                                 zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *text, size_t text_cap, size_t *text_used)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if ((rc = search_check_args(h, pattern, pattern_len, flags, digest, status, count, first))) return rc;
-    if ((rc = lines_check_args(h, pattern, pattern_len, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used))) return rc;
-    *rec_used = 0; *text_used = 0;
-    if (n == 0) return ZARC_GPU_OK;
-    if ((rc = search_upload_pattern(h, pattern, pattern_len, flags))) return rc;
-    LinesRun run;
-    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, nullptr, (uint8_t *)text, &run};
-    rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, pattern, pattern_len, flags, count, first, &ln);
-    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
-    return rc;
+    const LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used};
+    return search_call_host(h, n, frame, frame_len, raw_len, expect, MatcherArgs{Matcher::PATTERN, pattern, pattern_len, nullptr, flags}, &la,
+                            SearchOut{(uint8_t *)digest, status, count, first, nullptr, nullptr});
 }
-
-// zarc_gpu_search_batch's chunk loop with the set's kernels behind every chunk's verdict: 60 bytes per frame come back, and the hits
 int zarc_gpu_search_set_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                               const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const zarc_gpu_pattern_set *set, unsigned flags,
                               uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *which, uint64_t *hits)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if ((rc = search_set_check_args(h, set, flags, false, digest, status, count, first, which))) return rc;
-    if (hits) memset(hits, 0, set->count * sizeof *hits);
-    if (n == 0) return ZARC_GPU_OK;
-    if ((rc = search_upload_set(h, set, flags))) return rc;
-    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, 0, flags, count, first, nullptr, set, which, hits);
+    return search_call_host(h, n, frame, frame_len, raw_len, expect, MatcherArgs{Matcher::SET, nullptr, 0, set, flags}, nullptr,
+                            SearchOut{(uint8_t *)digest, status, count, first, which, hits});
 }
-// ... and with the line kernels behind every chunk's search
 int zarc_gpu_search_set_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                                     const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const zarc_gpu_pattern_set *set, unsigned flags, uint64_t max_lines,
                                     uint64_t max_line, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first,
                                     uint64_t *which, uint64_t *hits, uint64_t *lines, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *text,
                                     size_t text_cap, size_t *text_used)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    if ((rc = search_set_check_args(h, set, flags, true, digest, status, count, first, which))) return rc;
-    if ((rc = lines_check_args(h, "", 0, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used))) return rc;
-    *rec_used = 0; *text_used = 0;
-    if (hits) memset(hits, 0, set->count * sizeof *hits);
-    if (n == 0) return ZARC_GPU_OK;
-    if ((rc = search_upload_set(h, set, flags))) return rc;
-    LinesRun run;
-    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, nullptr, (uint8_t *)text, &run};
-    rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, 0, flags, count, first, &ln, set, which, hits);
-    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
-    return rc;
+    const LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used};
+    return search_call_host(h, n, frame, frame_len, raw_len, expect, MatcherArgs{Matcher::SET, nullptr, 0, set, flags}, &la,
+                            SearchOut{(uint8_t *)digest, status, count, first, which, hits});
 }
-// zarc_gpu_search_batch's chunk loop with the automaton's kernels behind every chunk's verdict
 int zarc_gpu_search_regex_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                                 const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *regex, size_t regex_len, unsigned flags,
                                 uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    zarc_gpu_regex_dfa dfa;
-    if ((rc = search_regex_check_args(h, regex, regex_len, flags, digest, status, count, first, &dfa))) return rc;
-    if (n == 0) return ZARC_GPU_OK;
-    if ((rc = search_upload_regex(h, &dfa))) return rc;
-    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, regex, regex_len, flags, count, first, nullptr, nullptr, nullptr, nullptr, true);
+    return search_call_host(h, n, frame, frame_len, raw_len, expect, MatcherArgs{Matcher::REGEX, regex, regex_len, nullptr, flags}, nullptr,
+                            SearchOut{(uint8_t *)digest, status, count, first, nullptr, nullptr});
 }
-// ... and with the line kernels behind every chunk's search
 int zarc_gpu_search_regex_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                                       const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *regex, size_t regex_len, unsigned flags, uint64_t max_lines,
                                       uint64_t max_line, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first,
                                       uint64_t *lines, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *text, size_t text_cap, size_t *text_used)
 {
-    int rc = check_common(h, n);
-    if (rc) return rc;
-    zarc_gpu_regex_dfa dfa;
-    if ((rc = search_regex_check_args(h, regex, regex_len, flags, digest, status, count, first, &dfa))) return rc;
-    if ((rc = lines_check_args(h, "", 0, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used))) return rc;
-    *rec_used = 0; *text_used = 0;
-    if (n == 0) return ZARC_GPU_OK;
-    if ((rc = search_upload_regex(h, &dfa))) return rc;
-    LinesRun run;
-    const LinesReq ln{max_lines, (uint32_t)max_line, lines, 0, rec, rec_cap, nullptr, (uint8_t *)text, &run};
-    rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, regex, regex_len, flags, count, first, &ln, nullptr, nullptr, nullptr, true);
-    *rec_used = run.rec_used; *text_used = (size_t)run.text_used;
-    return rc;
+    const LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used};
+    return search_call_host(h, n, frame, frame_len, raw_len, expect, MatcherArgs{Matcher::REGEX, regex, regex_len, nullptr, flags}, &la,
+                            SearchOut{(uint8_t *)digest, status, count, first, nullptr, nullptr});
 }
-
 
 // verify's way in and pack's way out around zarc_gpu_repack_batch_device, per staged chunk: chunk c+1's frames come in and chunk c-1's
 // new frames go out while chunk c is decoded and encoded.  Nothing else of content moves: the decoded bytes stay in the handle's scratch.
@@ -2840,11 +2818,8 @@ int zarc_gpu_repack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
     if (n == 0) return ZARC_GPU_OK;
     if (!frame || !frame_len || !raw_len || !dst || !dst_off || !dst_len || !digest || !status) return ZARC_GPU_E_PARAM;
     NestedCall nested(h);
+    if ((rc = check_frame_sizes(h, n, frame_len, raw_len, frame))) return rc;
     std::vector<uint64_t> in_sz(n), out_sz(n), weight(n), flen(n), rlen(n);
-    for (size_t i = 0; i < n; i++) {
-        if (frame_len[i] && !frame[i]) return ZARC_GPU_E_PARAM;
-        if ((uint64_t)frame_len[i] >= 0xFFFFFFF0ull || (uint64_t)raw_len[i] >= 0xFFFFFFF0ull) { set_error(h, "frames of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; } // before any size arithmetic or staging
-    }
     uint64_t need = 0;
     for (size_t i = 0; i < n; i++) {
         flen[i] = frame_len[i]; rlen[i] = raw_len[i];
