@@ -11,14 +11,15 @@ for f in *.hip; do
   # must be 0), and the vector-memory waits inside the level-3 kernel's tile loop (loop depth >= 3: units, blocks, tiles), full drains
   # (vmcnt(0)) against counted ones.  A kernel is taken to end at its first s_endpgm (today's finder kernels have one exit each): were
   # the compiler to emit an early exit, the waits behind it would be missing from the count.  Only the level-3 kernel is counted, so
-  # the two counters are never reset.
+  # the counters are never reset.  s_barrier: the workgroup barriers of that loop, rare paths included.
   if [ $f = zge_match.hip ]; then
     awk '/^_Z[0-9]+zarc_zge_match[a-z_]*9ZgeParams[A-Za-z0-9_]*:/ { k = $0; sub(/^_Z[0-9]+/, "", k); sub(/9ZgeParams.*/, "", k); d = 0 }
-         /s_endpgm/ { if (k != "") { printf " %s flat_: %d", k, fl[k]; if (k == "zarc_zge_match") printf "  tile loop vmcnt(0): %d  vmcnt(N>0): %d", z, c; printf "\n" } k = "" }
+         /s_endpgm/ { if (k != "") { printf " %s flat_: %d", k, fl[k]; if (k == "zarc_zge_match") printf "  tile loop vmcnt(0): %d  vmcnt(N>0): %d  s_barrier: %d", z, c, sb; printf "\n" } k = "" }
          k != "" && (/^\.LBB/ || /^; %bb\./) { d = 0; if (match($0, /Depth=[0-9]+/)) d = substr($0, RSTART + 6, RLENGTH - 6) + 0 }
          k != "" && /^[ \t]+flat_/ { fl[k]++ }
          k == "zarc_zge_match" && d >= 3 && /s_waitcnt/ && /vmcnt\(0\)/ { z++ }
-         k == "zarc_zge_match" && d >= 3 && /s_waitcnt/ && /vmcnt\([1-9]/ { c++ }' /tmp/spills_$$.s
+         k == "zarc_zge_match" && d >= 3 && /s_waitcnt/ && /vmcnt\([1-9]/ { c++ }
+         k == "zarc_zge_match" && d >= 3 && /^[ \t]+s_barrier/ { sb++ }' /tmp/spills_$$.s
   fi
 done
 rm -f /tmp/spills_$$.s

@@ -184,6 +184,15 @@ __device__ __forceinline__ uint32_t shfl_up1(uint32_t v)
     return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xF, 0xF, false); // wave_shr:1
 #endif
 }
+// the mirror: value of the lane above (lane 63 keeps its own)
+__device__ __forceinline__ uint32_t shfl_down1(uint32_t v)
+{
+#ifdef ZARC_HIPEMU
+    return shfl_down(v, 1u);
+#else
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x130, 0xF, 0xF, false); // wave_shl:1
+#endif
+}
 // inclusive prefix sum inside every 16-lane row (the first four steps of the scan above)
 __device__ __forceinline__ uint32_t row_scan_incl(uint32_t v)
 {

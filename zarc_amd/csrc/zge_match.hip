@@ -20,7 +20,9 @@
 //         lookups see the inserts of EARLIER tiles only -- the entries of tile T+1 are requested at the top of S3 of tile T, inserts are
 //         fire-and-forget atomic max behind the S4 barrier, so neither is on the tile's critical path and no order inside a tile is needed
 //   S4    backward propagation: position t may start the match found at t+k, k bytes earlier
-//   S5    one-byte lazy rule -> take flag and successor next[t] for every position
+//   S5    one-byte lazy rule -> take flag and successor next[t] for every position; the next position's final score comes from the
+//         next lane, for a wave's last position from a second evaluation of the first position of the next wave: no barrier
+//         between adoption and S5 (the deep finder, which looks two positions ahead, reads final matches from LDS behind one)
 //   S6    the greedy parse IS the path from the entry cursor through next[]: per 64-position chunk the exit of
 //         every position by 6 rounds of shuffle pointer-jumping, then the chunk entries by a short chain
 //         through LDS, then each wave marks its chunk's path with v_readlane -- no workgroup barriers
@@ -80,8 +82,9 @@ constexpr int TB_BYTES = 12 + REP_BACK_MAX + TILE + CAP_MAX + 24; // rep window 
 template <int TAB_LOG, bool NEAR16> struct MatchLds {
     static constexpr int TAB_WORDS = NEAR16 ? (1 << TAB_LOG) / 2 : 2 << TAB_LOG;
     uint32_t tab[TAB_WORDS + (NEAR16 ? 1 : 0)]; // NEAR16: one more word = slot 2^TAB_LOG, where positions without a hash look up and store (no branch in the chain)
-    uint32_t a0[TILE], a1[TILE]; // S1: hashes -> S2: candidates (pos+1) -> S3: a0 = own match (match_pack) -> S4: a1 = final match
+    uint32_t a0[TILE], a1[TILE]; // S1: hashes -> S2: candidates (pos+1) -> S3: a0 = own match (match_pack) -> S4: a1 = final match (deep finder)
     uint32_t ex[TILE];            // S4: best backward offer per position; S6: first position outside its chunk reached from each position
+                                  // (level-3 and fast finder: those exits go to a1 and ex keeps the offers to the end of the tile, see LAZY_BY_LANE)
     uint32_t tb[2][(TB_BYTES + 3) / 4]; // the window of a tile lives in buffer (tile / TILE) & 1: the current tile's and the next one's
     uint32_t wcnt[CHUNKS];       // S6: selected matches << 16 | literals of each chunk
     uint32_t wrep[2 * CHUNKS];   // S6 (level >= 9): offset of each chunk's last selected match, and of the last one different from it
@@ -229,6 +232,12 @@ __device__ __forceinline__ void zge_match_body(MatchLds<TAB_LOG, NEAR16> &L, con
     static_assert(FAR_BACK % 8 == 0 && FAR_BACK >= 8 && FAR_BACK <= 48, "backward extension of far candidates");
     static_assert(!FAR_CDC || (FAR_WAYS == 1 && !FAR_SHORT && far_shift >= FAR_CDC), "content-defined sampling: one way on the 12-byte hash");
     constexpr uint32_t cdc_mask = (1u << FAR_CDC) - 1;
+    // The lazy rule takes the next position's final score from the next lane instead of from LDS behind a barrier (zge_parse_round.h).
+    // Not the deep finder: LAZY2 looks two positions ahead and its rounds re-run the parse; it keeps the barrier and the a1[] round trip.
+    // The chunk exits of S6 then live in a1[] -- free with one near table once the thread's own far insert has read its word (program
+    // order), and until the next tile's S1 behind two barriers -- because ex[] must keep the offers for a wave that is still in adoption.
+    constexpr bool LAZY_BY_LANE = NEAR16 && !LAZY2 && !REP_PASS;
+    uint32_t *const Lexit = LAZY_BY_LANE ? L.a1 : L.ex;
     uint32_t *const Ltl = L.tab, *const Lts = L.tab + (NEAR16 ? 0 : (1 << TAB_LOG)); // long / short table (not NEAR16)
     typedef uint16_t __attribute__((may_alias)) u16a;
     u16a *const Lt16 = (u16a *)L.tab;                                                  // the 16-bit near table (NEAR16)

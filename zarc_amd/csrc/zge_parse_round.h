@@ -4,6 +4,7 @@
 // of the live recent-offset pass.  An include rather than a lambda or a loop around one copy: the level-3 kernel sits exactly at its
 // 128-register budget, and either form moved its spills (44 -> 72 / 108 bytes of scratch, 196 -> 221 ms on configs[1]).
 // Uses the locals of the tile loop; writes fo / fw (final match per position), msel / mlit (the path's matches / literals per chunk).
+// Workgroup barriers of one pass: S4, [deep finder: adoption -> S5,] S6a -> S6b, S6 -> S7.
             // ---- S4: backward propagation.  A position whose match extends b bytes backwards offers it to the b
             // positions before it (ds_max of score << 6 | 63-k: best score wins, then the nearest source); every position
             // then adopts the best offer if it beats its own match.  Same result as scanning the 8 following positions.
@@ -87,27 +88,51 @@
             }
             cold = 0;
 #endif
+            // Adoption.  fsc = the score of the final match (0: none; a match, own or adopted, scores above 0).  An adopted offer IS that
+            // score: the offer of a match (len, off) from k positions behind is score(len, off) + LITC * k, and the score is linear in the
+            // length with slope LITC (score_mc), so it equals score(len + k, off), the score of the match as this position starts it.
+            int32_t fsc[PER];
 #pragma unroll
             for (int u = 0; u < PER; u++) {
                 const uint32_t idx = ZGE_IDX(u);
                 const uint32_t offer = L.ex[idx];
                 uint32_t blen_ = mw[u] & 0xFFFF, boff = mo[u];
                 bool brep = (mw[u] >> 24) & 1;
-                if (offer) {
-                    const int32_t own = blen_ ? score_of(P, blen_, boff, brep) : 0;
-                    if ((int32_t)(offer >> 6) > own) {
-                        const uint32_t k = 63u - (offer & 63u);
-                        const uint32_t nm = L.a0[idx + k];
-                        boff = match_off(nm);
-                        blen_ = match_len(nm) + k;
-                        brep = match_rep(nm);
-                    }
+                int32_t fs = blen_ ? score_of(P, blen_, boff, brep) : 0;
+                if (offer && (int32_t)(offer >> 6) > fs) {
+                    const uint32_t k = 63u - (offer & 63u);
+                    const uint32_t nm = L.a0[idx + k];
+                    boff = match_off(nm);
+                    blen_ = match_len(nm) + k;
+                    brep = match_rep(nm);
+                    fs = (int32_t)(offer >> 6);
                 }
                 fo[u] = boff;
                 fw[u] = blen_ | ((brep ? 1u : 0u) << 24);
-                L.a1[idx] = match_pack(boff, blen_, brep); // final match (a1 held this thread's short candidate until S3)
+                fsc[u] = fs;
+                if (!LAZY_BY_LANE) L.a1[idx] = match_pack(boff, blen_, brep); // final match (a1 held this thread's short candidate until S3)
             }
-            zd::lds_barrier();
+            // LAZY_BY_LANE (the level-3 and the fast finder): the lazy rule needs the final score of the NEXT position, which is the next
+            // lane's -- a lane shift -- except behind a chunk: lane 63 of the first chunk takes lane 0 of the second, and lane 63 of the
+            // second needs position 128 (wave + 1), another wave's.  Everything that decides that one is final behind the S4 barrier
+            // (its offer in ex[], its own match in a0[], the rule above), so this wave works it out once more: no barrier in front of
+            // S5, no final matches through a1[].  ex[] therefore keeps the offers until the next tile's S1: the chunk exits go to a1[].
+            int32_t nsc[PER] = {0, 0};
+            if (LAZY_BY_LANE && P.lazy) { // (uniform: the fast finder has no lazy step and asks for no neighbour)
+                const uint32_t e = (uint32_t)(wave + 1) * (uint32_t)(PER * 64); // uniform
+                int32_t edge = 0;
+                if (e < tcount) {
+                    const uint32_t offer = L.ex[e], em = L.a0[e];
+                    const uint32_t el = match_len(em);
+                    edge = el ? score_of(P, el, match_off(em), match_rep(em)) : 0;
+                    if (offer && (int32_t)(offer >> 6) > edge) edge = (int32_t)(offer >> 6);
+                }
+                const int32_t first1 = (int32_t)zd::readlane((uint32_t)fsc[1], 0);
+                const int32_t above0 = (int32_t)zd::shfl_down1((uint32_t)fsc[0]), above1 = (int32_t)zd::shfl_down1((uint32_t)fsc[1]); // (whole wave)
+                nsc[0] = lane == 63 ? first1 : above0;
+                nsc[1] = lane == 63 ? edge : above1;
+            } else if (!LAZY_BY_LANE)
+                zd::lds_barrier(); // the final matches of every wave are in a1
             ZGE_PROF(5);
             // ---- S5: take flag (one-byte lazy lookahead inside the tile) and successor ----
             bool take[PER];
@@ -117,21 +142,25 @@
                 const uint32_t idx = ZGE_IDX(u);
                 const uint32_t my_len = fw[u] & 0xFFFF;
                 take[u] = idx < tcount && my_len != 0;
-                if (take[u] && P.lazy && idx + 1 < tcount) {
-                    const uint32_t m2 = L.a1[idx + 1];
-                    const uint32_t l2 = match_len(m2);
-                    if (l2 && score_of(P, l2, match_off(m2), match_rep(m2)) > score_of(P, my_len, fo[u], (fw[u] >> 24) & 1) + F_LAZY_DELTA) take[u] = false;
-                }
-                if (LAZY2 && take[u] && idx + 2 < tcount) { // two bytes ahead (libzstd's lazy2)
-                    const uint32_t m3 = L.a1[idx + 2];
-                    const uint32_t l3 = match_len(m3);
-                    if (l3 && score_of(P, l3, match_off(m3), match_rep(m3)) > score_of(P, my_len, fo[u], (fw[u] >> 24) & 1) + LAZY2) take[u] = false;
+                if (LAZY_BY_LANE) {
+                    if (take[u] && P.lazy && idx + 1 < tcount && nsc[u] > fsc[u] + F_LAZY_DELTA) take[u] = false;
+                } else {
+                    if (take[u] && P.lazy && idx + 1 < tcount) {
+                        const uint32_t m2 = L.a1[idx + 1];
+                        const uint32_t l2 = match_len(m2);
+                        if (l2 && score_of(P, l2, match_off(m2), match_rep(m2)) > fsc[u] + F_LAZY_DELTA) take[u] = false;
+                    }
+                    if (LAZY2 && take[u] && idx + 2 < tcount) { // two bytes ahead (libzstd's lazy2)
+                        const uint32_t m3 = L.a1[idx + 2];
+                        const uint32_t l3 = match_len(m3);
+                        if (l3 && score_of(P, l3, match_off(m3), match_rep(m3)) > fsc[u] + LAZY2) take[u] = false;
+                    }
                 }
                 nx[u] = take[u] ? idx + my_len : idx + 1;
             }
             // ---- S6a: per chunk, the first position outside the chunk reached from every position; for the first chunk of the
-            // wave's pair this is carried on through the second chunk (one more shuffle), so ex[] of a pair's first half holds
-            // the exit of the whole pair ----
+            // wave's pair this is carried on through the second chunk (one more shuffle), so the exit array (Lexit: a1[] with
+            // LAZY_BY_LANE, else ex[]) of a pair's first half holds the exit of the whole pair ----
             {
                 uint32_t val[PER];
 #pragma unroll
@@ -151,19 +180,19 @@
                     if (val[0] >= obase && val[0] < oend) val[0] = through;
                 }
 #pragma unroll
-                for (int u = 0; u < PER; u++) L.ex[ZGE_IDX(u)] = val[u];
+                for (int u = 0; u < PER; u++) Lexit[ZGE_IDX(u)] = val[u];
             }
             zd::lds_barrier();
             ZGE_PROF(6);
-            // ---- S6b/c + S7: chunk entries by a chain through ex[], path marks per chunk, emission ----
+            // ---- S6b/c + S7: chunk entries by a chain through the exit array, path marks per chunk, emission ----
             {
                 zd::wave_priority<2>(); // a serial chain (LDS hops, then a scalar walk): latency matters here, not throughput
                 uint32_t cur = (uint32_t)((pos > tile ? pos : tile) - tile);
                 int c = 0;
 #pragma unroll
-                for (; c < wave; c++) { // pairs of chunks before mine: hop over them (an entry in either half leaves through ex[])
+                for (; c < wave; c++) { // pairs of chunks before mine: hop over them (an entry in either half leaves through the exit array)
                     const uint32_t pend = (uint32_t)(c * 128 + 128) < tcount ? (uint32_t)(c * 128 + 128) : tcount;
-                    if (cur < pend) cur = L.ex[cur];
+                    if (cur < pend) cur = Lexit[cur];
                 }
                 cur = zd::uniform(cur);
 #pragma unroll
