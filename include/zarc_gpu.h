@@ -46,7 +46,8 @@ extern "C" {
                                   same reason, and zarc_gpu_search_batch* with ZARC_GPU_T_SEARCH after them (ZARC_GPU_T_COUNT grew from 10 to 11:
                                   zarc_gpu_last_kernel_ms of an older library answers < 0 for the new id, as for any id it does not know), and
                                   zarc_gpu_search_lines_batch* with ZARC_GPU_T_LINES after those (ZARC_GPU_T_COUNT grew from 11 to 12), then
-                                  zarc_gpu_search_set_*, and zarc_gpu_regex_compile with zarc_gpu_search_regex_* (new symbols; ZARC_GPU_T_COUNT stays 12) */
+                                  zarc_gpu_search_set_*, and zarc_gpu_regex_compile with zarc_gpu_search_regex_* (new symbols; ZARC_GPU_T_COUNT stays 12), then
+                                  zarc_gpu_select_lines_batch* (new symbols and types; nothing existing changes) */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -464,6 +465,56 @@ int zarc_gpu_search_regex_lines_batch_device(zarc_gpu_t *h, size_t n, const void
                                              int *status, uint64_t *count, uint64_t *first, uint64_t *lines, zarc_gpu_line *rec /* HOST array */,
                                              size_t rec_cap, size_t *rec_used, void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
 
+/* ---- search, selected lines: the lines a search does NOT match, and the lines around a hit ------------------------------------------------ */
+/* What `grep -v` and `grep -A / -B / -C` print: one pair of calls behind all three matchers.  A LINE and a matching start position are
+ * defined as in zarc_gpu_search_lines_batch (a set: zarc_gpu_search_set_lines_batch; a regex: zarc_gpu_search_regex_batch).  For frame i
+ * with lines 1 .. L:
+ *   - M = the lines that hold at least one matching start position.  H, the HIT lines, = M, or {1 .. L} \ M with ZARC_GPU_SELECT_INVERT.
+ *     Empty lines exist and never match, so under INVERT they are hits.  Content ending in 0x0A has no extra last line, an empty frame has
+ *     no line, "\n" is one empty line.
+ *   - S, the SELECTED lines, = { l in 1 .. L : some h in H with h - before <= l <= h + after }.  The arithmetic saturates: before and after
+ *     are uint32_t and any value is legal (0xFFFFFFFF: every line of a frame with a hit, none of a frame without).
+ *   - status, digest, count, first -- for a set, which and hits as well -- are EXACTLY the matcher's plain search call: INVERT does not
+ *     touch them.  lines[i] = |H| and selected[i] = |S|, both whatever the caps.  A frame that did not decode: 0 and 0, no record.
+ *   - Delivery is zarc_gpu_search_lines_batch's rule over S: frames in batch order, frame i delivers its first d_i = min(selected[i],
+ *     max_lines (0 = no limit), rec_cap - sum of d_j, j < i) lines of S in ascending `start`.  Records are zarc_gpu_line; `match` is the lowest
+ *     matching start position in the line, or ZARC_GPU_SEARCH_NONE when the line holds none.  A record is a hit line iff
+ *     (match != ZARC_GPU_SEARCH_NONE) != invert; every other record is context.  text, text_cap, max_line and both ZARC_GPU_E_DSTSIZE rules
+ *     are zarc_gpu_search_lines_batch's.
+ *   - The matcher: kind FIXED (text, text_len = the pattern), SET (set) or REGEX (text, text_len = the expression); flags
+ *     (ZARC_GPU_SEARCH_ICASE) and the arguments of that kind exactly as its own lines call takes them.  which and hits may be NULL; non-NULL
+ *     with a kind other than SET is ZARC_GPU_E_PARAM.
+ *   - Checks, codes and messages: those of the matcher's own lines call, in its order; then, as ZARC_GPU_E_PARAM, an unknown select flag,
+ *     reserved != 0, a missing `selected`.  A missing matcher or selection and an unknown kind are ZARC_GPU_E_PARAM as well.
+ *   - With flags == 0 && before == 0 && after == 0, lines, selected (== lines) and every record equal the matcher's own lines call byte for
+ *     byte.  Results are the same for every ZARC_GPU_PX_SCRATCH_MB, every chunking, host and device form and every number of handles.
+ *   - zarc_gpu_last_copy_bytes: as zarc_gpu_search_lines_batch (D2H = *text_used).  zarc_gpu_last_kernel_ms: ZARC_GPU_T_LINES covers
+ *     zarc_lines_select_* with zarc_lines_scan and zarc_lines_gather.
+ *   - Cost: the content is read by the matcher once to mark and once more, in the slices that deliver, to emit -- as the lines calls.  Under
+ *     INVERT or with wide context most slices deliver. */
+enum { ZARC_GPU_MATCH_FIXED = 0, ZARC_GPU_MATCH_SET = 1, ZARC_GPU_MATCH_REGEX = 2 };
+enum { ZARC_GPU_SELECT_INVERT = 1 };              /* zarc_gpu_line_select.flags; any other bit: ZARC_GPU_E_PARAM */
+typedef struct {
+    uint32_t kind;                   /* ZARC_GPU_MATCH_* */
+    uint32_t flags;                  /* ZARC_GPU_SEARCH_ICASE */
+    const void *text;                /* FIXED: the pattern; REGEX: the expression (HOST memory) */
+    size_t text_len;
+    const zarc_gpu_pattern_set *set; /* SET */
+} zarc_gpu_matcher;
+typedef struct { uint32_t flags, before, after, reserved; } zarc_gpu_line_select;
+int zarc_gpu_select_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const zarc_gpu_matcher *matcher,
+                                const zarc_gpu_line_select *select, uint64_t max_lines /* per frame; 0 = no limit */, uint64_t max_line /* 1..65536 */,
+                                uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *which /* SET, or NULL */,
+                                uint64_t *hits /* SET, or NULL */, uint64_t *lines /* n */, uint64_t *selected /* n */, zarc_gpu_line *rec, size_t rec_cap,
+                                size_t *rec_used, void *text, size_t text_cap, size_t *text_used);
+int zarc_gpu_select_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                       const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const zarc_gpu_matcher *matcher /* HOST */,
+                                       const zarc_gpu_line_select *select, uint64_t max_lines, uint64_t max_line, uint8_t *digest /* n*32 */, int *status,
+                                       uint64_t *count, uint64_t *first, uint64_t *which /* SET, or NULL */, uint64_t *hits /* SET, or NULL */,
+                                       uint64_t *lines, uint64_t *selected, zarc_gpu_line *rec /* HOST array */, size_t rec_cap, size_t *rec_used,
+                                       void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
+
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN]);
@@ -489,7 +540,7 @@ enum {
     ZARC_GPU_T_DEC_LITS = 8,  /* decoder stage 2: Huffman literals (zarc_zdec_literals, side stream)      */
     ZARC_GPU_T_DEC_FRAMES = 9,/* decoder frame pass (zarc_zstd_frames + the inline decoder for the rest)  */
     ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan (a set: zarc_set_scan and zarc_set_which; a regex: zarc_regex_summary, _carry and _scan), summed over the parts of a call; < 0 or 0 after any other call */
-    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set or a regex: its twins of mark and emit), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set or a regex: its twins of mark and emit; select_lines: zarc_lines_select_* in place of mark, carry and emit), summed over the parts of a call; < 0 or 0 after any other call */
     ZARC_GPU_T_COUNT = 12
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);

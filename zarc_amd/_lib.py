@@ -39,6 +39,8 @@ T_LINES = 11   # zarc_lines_* of a search_lines call (summed over its parts)
 SEARCH_ICASE, SEARCH_MAX_PATTERN, SEARCH_NONE = 1, 256, 2 ** 64 - 1
 SEARCH_MAX_SET = 1024  # zarc_gpu_search_set_*: the largest set
 LINES_MAX_LINE = 65536  # zarc_gpu_search_lines_batch*: the largest max_line
+MATCH_FIXED, MATCH_SET, MATCH_REGEX = 0, 1, 2  # zarc_gpu_select_lines_batch*: zarc_gpu_matcher.kind
+SELECT_INVERT = 1  # ... and zarc_gpu_line_select.flags
 REGEX_MAX_PATTERN, REGEX_MAX_STATES = 1024, 64  # zarc_gpu_search_regex_*: the longest expression, the most states of its automaton
 
 EXPORTS = [
@@ -49,7 +51,7 @@ EXPORTS = [
     "zarc_gpu_search_batch", "zarc_gpu_search_batch_device", "zarc_gpu_search_lines_batch", "zarc_gpu_search_lines_batch_device",
     "zarc_gpu_search_set_batch", "zarc_gpu_search_set_batch_device", "zarc_gpu_search_set_lines_batch", "zarc_gpu_search_set_lines_batch_device",
     "zarc_gpu_regex_compile", "zarc_gpu_search_regex_batch", "zarc_gpu_search_regex_batch_device", "zarc_gpu_search_regex_lines_batch",
-    "zarc_gpu_search_regex_lines_batch_device",
+    "zarc_gpu_search_regex_lines_batch_device", "zarc_gpu_select_lines_batch", "zarc_gpu_select_lines_batch_device",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -88,6 +90,29 @@ class PatternSet(ctypes.Structure):
             at += len(p)
         s.bytes, s.off, s.len, s.count = ctypes.cast(s._blob, ctypes.c_void_p), s._off, s._len, n
         return s
+
+
+class MatcherDesc(ctypes.Structure):
+    """zarc_gpu_matcher: what a select_lines call searches for (host memory)"""
+    _fields_ = [("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("text", ctypes.c_void_p), ("text_len", ctypes.c_size_t), ("set", ctypes.POINTER(PatternSet))]
+
+    @classmethod
+    def of(cls, kind, what, flags=0):
+        """-> the structure over `what` (FIXED / REGEX: bytes; SET: a list of bytes); it keeps what it points to alive"""
+        m = cls()
+        m.kind, m.flags = kind, flags
+        if kind == MATCH_SET:
+            m._set = PatternSet.of(what)
+            m.set = ctypes.pointer(m._set)
+        else:
+            m._text = ctypes.create_string_buffer(bytes(what), max(len(what), 1))
+            m.text, m.text_len = ctypes.cast(m._text, ctypes.c_void_p), len(what)
+        return m
+
+
+class LineSelect(ctypes.Structure):
+    """zarc_gpu_line_select: which lines a select_lines call delivers"""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("flags", "before", "after", "reserved")]
 
 
 class RegexDfa(ctypes.Structure):
@@ -161,6 +186,11 @@ def load(path=None):
     lib.zarc_gpu_search_regex_batch_device.argtypes = lib.zarc_gpu_search_batch_device.argtypes
     lib.zarc_gpu_search_regex_lines_batch.argtypes = lib.zarc_gpu_search_lines_batch.argtypes
     lib.zarc_gpu_search_regex_lines_batch_device.argtypes = lib.zarc_gpu_search_lines_batch_device.argtypes
+    mp, qp = c.POINTER(MatcherDesc), c.POINTER(LineSelect)
+    lib.zarc_gpu_select_lines_batch.argtypes = [vp, sz, vpp, szp, szp, vp, mp, qp, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, u64p, u64p, u64p, lp, sz, szp,
+                                                vp, sz, szp]
+    lib.zarc_gpu_select_lines_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, mp, qp, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, u64p, u64p, u64p,
+                                                       lp, sz, szp, vp, sz, szp]
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

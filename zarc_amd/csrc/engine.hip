@@ -126,6 +126,8 @@ struct zarc_gpu {
     DevBuf d_ln_slices, d_ln_lines;             // ZarcLineSlice of every slice; matching lines of every frame (decoder order)
     DevBuf d_ln_base, d_ln_deliver;             // what the host decided: first record and number of records of every frame (decoder order)
     DevBuf d_ln_rec, d_ln_total, d_ln_text;     // the part's records, the sum of their text_len, and (host form) their text: sized by what the part delivers
+    // the selected lines (zarc_gpu_select_lines_batch*): zarc_lines_select_* in place of zarc_lines_mark / _carry / _emit
+    DevBuf d_sel_slices, d_sel_count;           // ZarcSelSlice of every slice; selected lines of every frame (decoder order; the hit lines go to d_ln_lines)
     bool vout_busy = false;     // a repack pass is between its halves: d_vout is not the check's to take
     uint64_t dec_scratch = 0;   // decoder scratch (sequences, literals, tables) of the most recent decode, as counted against the budget
     // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
@@ -649,6 +651,9 @@ struct LinesReq {
     uint8_t *d_text;           // device form: the caller's text buffer
     uint8_t *h_text;           // host form: the caller's text buffer (the part's text is gathered into scratch of the handle first)
     LinesRun *run;
+    bool select;               // zarc_gpu_select_lines_batch* with an ACTIVE selection: deliver the selected lines `sel` describes; lines[] counts the hit lines
+    ZarcSelect sel;
+    uint64_t *selected;        // zarc_gpu_select_lines_batch*; host, as lines (an inactive selection: the plain kernels run, selected == lines)
 };
 // What to search for, as search_prepare has put it on the device: one of three kinds, each with the fields its kernels take
 struct Matcher {
@@ -674,7 +679,7 @@ SearchReq part_of(SearchReq r, size_t a)
 {
     r.count += a; r.first += a;
     if (r.which) r.which += a;
-    if (r.lines) { r.ln.lines += a; r.ln.frame0 += a; }
+    if (r.lines) { r.ln.lines += a; r.ln.frame0 += a; if (r.ln.selected) r.ln.selected += a; }
     return r;
 }
 int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
@@ -1174,7 +1179,7 @@ struct SearchPart {
     size_t set_lds = 0;                // SET: bytes of the set's image in LDS
     int e5 = -1, e6 = -1, e7 = -1;     // timer marks: in front of the scan, behind it, behind the first half of the lines
     float lines_ms2 = 0;               // the second half of the lines
-    std::vector<uint32_t> count, first, which, hits, lines; // what search_collect asked back (decoder order), for search_scatter
+    std::vector<uint32_t> count, first, which, hits, lines, selected; // what search_collect asked back (decoder order), for search_scatter
 };
 
 // search: the decoded bytes are judged; look through those of the frames that decoded, where they lie
@@ -1237,6 +1242,31 @@ int lines_mark(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
     ZHIP(h->d_ln_lines.reserve(p.n * 4));
     ZarcLineSlice *const d_ln = h->d_ln_slices.as<ZarcLineSlice>();
     uint32_t *const d_lines = h->d_ln_lines.as<uint32_t>();
+    if (srch.ln.select) { // the selected lines: a line belongs to the slice in which it ends, the carry counts hits and selected lines
+        const ZarcSelect q = srch.ln.sel;
+        ZHIP(h->d_sel_slices.reserve(sp.slices * sizeof(ZarcSelSlice)));
+        ZHIP(h->d_sel_count.reserve(p.n * 4));
+        ZarcSelSlice *const d_sel = h->d_sel_slices.as<ZarcSelSlice>();
+        switch (mt.kind) {
+        case Matcher::PATTERN:
+            hipLaunchKernelGGL(zarc_lines_select_mark, per_slice, dim3(256), 0, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, mt.pattern.d_bytes,
+                               mt.pattern.m, mt.icase, q, d_sel);
+            break;
+        case Matcher::SET:
+            hipLaunchKernelGGL(zarc_lines_select_mark_set, per_slice, dim3(256), sp.set_lds, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, *mt.set,
+                               h->d_set.as<uint32_t>(), mt.icase, q, d_sel);
+            break;
+        case Matcher::REGEX:
+            hipLaunchKernelGGL(zarc_lines_select_mark_regex, per_slice, dim3(256), 0, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, mt.d_regex,
+                               h->d_re_entry.as<uint8_t>(), q, d_sel);
+            break;
+        }
+        hipLaunchKernelGGL(zarc_lines_select_carry, dim3((unsigned)((p.n + 3) / 4)), dim3(256), 0, h->stream, n, d_slices, d_raw, q, d_sel, d_lines,
+                           h->d_sel_count.as<uint32_t>());
+        ZHIP(hipGetLastError());
+        ZHIP(p.t.mark(&sp.e7));
+        return ZARC_GPU_OK;
+    }
     switch (mt.kind) {
     case Matcher::PATTERN:
         hipLaunchKernelGGL(zarc_lines_mark, per_slice, dim3(256), 0, h->stream, n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, mt.pattern.d_bytes, mt.pattern.m,
@@ -1272,6 +1302,7 @@ int search_collect(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
         if (srch.hits) { sp.hits.resize(srch.match.set->count); ZHIP(hipMemcpyAsync(sp.hits.data(), h->d_set_hits.p, sp.hits.size() * 4, hipMemcpyDeviceToHost, h->stream)); }
     }
     if (srch.lines) { sp.lines.resize(n); ZHIP(hipMemcpyAsync(sp.lines.data(), h->d_ln_lines.p, n * 4, hipMemcpyDeviceToHost, h->stream)); }
+    if (srch.lines && srch.ln.select) { sp.selected.resize(n); ZHIP(hipMemcpyAsync(sp.selected.data(), h->d_sel_count.p, n * 4, hipMemcpyDeviceToHost, h->stream)); }
     return ZARC_GPU_OK;
 }
 void search_scatter(const DecodedPart &p, const SearchReq &srch, const SearchPart &sp)
@@ -1300,7 +1331,8 @@ int lines_deliver(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
     for (size_t c = 0; c < n; c++) {
         const uint32_t i = where[c];
         ln.lines[c] = sp.lines[i];
-        uint64_t d = sp.lines[i];
+        if (ln.selected) ln.selected[c] = ln.select ? sp.selected[i] : sp.lines[i];
+        uint64_t d = ln.select ? sp.selected[i] : sp.lines[i];
         if (ln.max_lines && d > ln.max_lines) d = ln.max_lines;
         d = std::min<uint64_t>(d, ln.rec_cap - run.rec_used - nrec);
         base[i] = nrec; deliver[i] = (uint32_t)d;
@@ -1319,6 +1351,23 @@ int lines_deliver(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
     const ZarcLineSlice *const d_ln = h->d_ln_slices.as<ZarcLineSlice>();
     const uint32_t *const d_deliver = h->d_ln_deliver.as<uint32_t>();
     ZarcLineRec *const d_rec = h->d_ln_rec.as<ZarcLineRec>();
+    if (ln.select) {
+        const ZarcSelSlice *const d_sel = h->d_sel_slices.as<ZarcSelSlice>();
+        switch (mt.kind) {
+        case Matcher::PATTERN:
+            hipLaunchKernelGGL(zarc_lines_select_emit, per_slice, dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, mt.pattern.d_bytes,
+                               mt.pattern.m, mt.icase, ln.sel, d_sel, d_rbase, d_deliver, ln.max_line, d_rec);
+            break;
+        case Matcher::SET:
+            hipLaunchKernelGGL(zarc_lines_select_emit_set, per_slice, dim3(256), sp.set_lds, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, *mt.set,
+                               h->d_set.as<uint32_t>(), mt.icase, ln.sel, d_sel, d_rbase, d_deliver, ln.max_line, d_rec);
+            break;
+        case Matcher::REGEX:
+            hipLaunchKernelGGL(zarc_lines_select_emit_regex, per_slice, dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, mt.d_regex,
+                               h->d_re_entry.as<uint8_t>(), ln.sel, d_sel, d_rbase, d_deliver, ln.max_line, d_rec);
+            break;
+        }
+    } else
     switch (mt.kind) {
     case Matcher::PATTERN:
         hipLaunchKernelGGL(zarc_lines_emit, per_slice, dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, mt.pattern.d_bytes, mt.pattern.m, mt.icase,
@@ -1991,6 +2040,8 @@ struct LinesArgs {
     size_t rec_cap, *rec_used;
     void *text;                       // device form: on the device; host form: the caller's memory
     size_t text_cap, *text_used;
+    const zarc_gpu_line_select *select = nullptr; // zarc_gpu_select_lines_batch*
+    uint64_t *selected = nullptr;
 };
 
 // Every check of a search call that does not look at the frames, in the order the callers are promised (the matcher, the flags, the result
@@ -2032,12 +2083,22 @@ int search_prepare(zarc_gpu_t *h, size_t n, const MatcherArgs &a, const SearchOu
         if (la->max_line < 1 || la->max_line > ZARC_GPU_LINES_MAX_LINE) { set_error(h, "search_lines: max_line is 1 to 65536"); return ZARC_GPU_E_PARAM; }
         if (a.kind == Matcher::PATTERN && memchr(a.text, 0x0A, a.text_len)) { set_error(h, "search_lines: the pattern must not contain a newline"); return ZARC_GPU_E_PARAM; }
         if (la->rec_cap > SIZE_MAX / (size_t)la->max_line || la->text_cap < la->rec_cap * (size_t)la->max_line) { set_error(h, "search_lines: text_cap is below rec_cap * max_line"); return ZARC_GPU_E_DSTSIZE; }
+        if (la->select) {
+            if (la->select->flags & ~(uint32_t)ZARC_GPU_SELECT_INVERT) { set_error(h, "select_lines: unknown select flag"); return ZARC_GPU_E_PARAM; }
+            if (la->select->reserved) { set_error(h, "select_lines: reserved must be 0"); return ZARC_GPU_E_PARAM; }
+            if (!la->selected) return ZARC_GPU_E_PARAM;
+        }
         *la->rec_used = 0; *la->text_used = 0;
     }
     if (a.kind == Matcher::SET && out.hits) memset(out.hits, 0, a.set->count * sizeof *out.hits); // (every part adds to them)
     *req = SearchReq{Matcher{a.kind, a.flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, {}}, out.count, out.first, out.which, out.hits, la != nullptr, LinesReq{}};
     if (la) req->ln = LinesReq{la->max_lines, (uint32_t)la->max_line, la->lines, 0, la->rec, la->rec_cap, host_text ? nullptr : (uint8_t *)la->text,
-                               host_text ? (uint8_t *)la->text : nullptr, run};
+                               host_text ? (uint8_t *)la->text : nullptr, run, false, ZarcSelect{0, 0, 0}, nullptr};
+    if (la && la->select) {
+        req->ln.select = la->select->flags || la->select->before || la->select->after;
+        req->ln.sel = ZarcSelect{la->select->flags & ZARC_GPU_SELECT_INVERT ? 1u : 0u, la->select->before, la->select->after};
+        req->ln.selected = la->selected;
+    }
     if (n == 0) return 0;
     switch (a.kind) {
     case Matcher::PATTERN: { // folded here when the text is folded there ('A'..'Z' only)
@@ -2057,6 +2118,20 @@ int search_prepare(zarc_gpu_t *h, size_t n, const MatcherArgs &a, const SearchOu
         req->match.d_regex = h->d_regex.as<ZarcRegexDfa>();
         return 0;
     }
+    return 0;
+}
+
+// zarc_gpu_select_lines_batch*: the matcher description as the arguments of that kind's own lines call
+int select_matcher(zarc_gpu_t *h, const zarc_gpu_matcher *m, const zarc_gpu_line_select *select, const uint64_t *which, const uint64_t *hits, MatcherArgs *a)
+{
+    if (!m || !select) { set_error(h, "select_lines: a matcher and a selection are needed"); return ZARC_GPU_E_PARAM; }
+    switch (m->kind) {
+    case ZARC_GPU_MATCH_FIXED: *a = MatcherArgs{Matcher::PATTERN, m->text, m->text_len, nullptr, m->flags}; break;
+    case ZARC_GPU_MATCH_SET: *a = MatcherArgs{Matcher::SET, nullptr, 0, m->set, m->flags}; break;
+    case ZARC_GPU_MATCH_REGEX: *a = MatcherArgs{Matcher::REGEX, m->text, m->text_len, nullptr, m->flags}; break;
+    default: set_error(h, "select_lines: unknown matcher kind"); return ZARC_GPU_E_PARAM;
+    }
+    if (m->kind != ZARC_GPU_MATCH_SET && (which || hits)) { set_error(h, "select_lines: which and hits belong to a set"); return ZARC_GPU_E_PARAM; }
     return 0;
 }
 
@@ -2129,6 +2204,22 @@ int zarc_gpu_search_regex_lines_batch_device(zarc_gpu_t *h, size_t n, const void
     const LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used};
     return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, MatcherArgs{Matcher::REGEX, regex, regex_len, nullptr, flags}, &la,
                               SearchOut{digest, status, count, first, nullptr, nullptr});
+}
+
+int zarc_gpu_select_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                       const uint64_t *raw_len, const uint8_t *expect, const zarc_gpu_matcher *matcher, const zarc_gpu_line_select *select,
+                                       uint64_t max_lines, uint64_t max_line, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, uint64_t *which,
+                                       uint64_t *hits, uint64_t *lines, uint64_t *selected, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used, void *d_text,
+                                       size_t text_cap, size_t *text_used)
+{
+    MatcherArgs a;
+    int rc = check_common(h, n);
+    if (rc || (rc = select_matcher(h, matcher, select, which, hits, &a))) return rc;
+    LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, d_text, text_cap, text_used};
+    la.select = select; la.selected = selected;
+    std::vector<uint64_t> own_which; // a set without `which`: the search still computes it
+    if (a.kind == Matcher::SET && !which) { own_which.resize(n + 1); which = own_which.data(); }
+    return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, a, &la, SearchOut{digest, status, count, first, which, hits});
 }
 
 int zarc_gpu_regex_compile(const void *regex, size_t regex_len, unsigned flags, zarc_gpu_regex_dfa *out, char *err, size_t err_cap)
@@ -2805,6 +2896,22 @@ int zarc_gpu_search_regex_lines_batch(zarc_gpu_t *h, size_t n, const void *const
     const LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used};
     return search_call_host(h, n, frame, frame_len, raw_len, expect, MatcherArgs{Matcher::REGEX, regex, regex_len, nullptr, flags}, &la,
                             SearchOut{(uint8_t *)digest, status, count, first, nullptr, nullptr});
+}
+
+int zarc_gpu_select_lines_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const zarc_gpu_matcher *matcher, const zarc_gpu_line_select *select,
+                                uint64_t max_lines, uint64_t max_line, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first,
+                                uint64_t *which, uint64_t *hits, uint64_t *lines, uint64_t *selected, zarc_gpu_line *rec, size_t rec_cap, size_t *rec_used,
+                                void *text, size_t text_cap, size_t *text_used)
+{
+    MatcherArgs a;
+    int rc = check_common(h, n);
+    if (rc || (rc = select_matcher(h, matcher, select, which, hits, &a))) return rc;
+    LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used};
+    la.select = select; la.selected = selected;
+    std::vector<uint64_t> own_which; // a set without `which`: the search still computes it
+    if (a.kind == Matcher::SET && !which) { own_which.resize(n + 1); which = own_which.data(); }
+    return search_call_host(h, n, frame, frame_len, raw_len, expect, a, &la, SearchOut{(uint8_t *)digest, status, count, first, which, hits});
 }
 
 // verify's way in and pack's way out around zarc_gpu_repack_batch_device, per staged chunk: chunk c+1's frames come in and chunk c-1's

@@ -264,6 +264,42 @@ __global__ void zarc_lines_mark_regex(uint32_t n, const uint64_t *slice_prefix, 
 __global__ void zarc_lines_emit_regex(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
                                       const ZarcRegexDfa *dfa, const uint8_t *entry, const ZarcLineSlice *slices, const uint64_t *rec_base,
                                       const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
+// the selected lines of a search (zdec_select.hip): the lines within `before` in front of and `after` behind a hit line -- a matching line,
+// with invert a line without a match.  A line belongs to the slice in which it ends.  ZarcSelSlice: what zarc_lines_select_mark* finds in a
+// slice and what zarc_lines_select_carry makes of it with the slices around (positions as in ZarcLineSlice; numbers are line numbers)
+struct ZarcSelect { uint32_t invert, before, after; };
+struct ZarcSelSlice {
+    uint32_t nl_count, first_nl, last_nl; // mark: 0x0A bytes of the slice, the first and the last one
+    uint32_t flags;                       // mark: 1 = a match in front of the first 0x0A, 2 = behind the last (no 0x0A: anywhere), 8 = the frame's
+                                          // unterminated last line ends here; carry: 4 = the line open at the slice's start holds a match in an earlier slice
+    uint32_t hits, first_hit, last_hit;   // mark: of the lines that end in the slice, the first one left out: hit lines, the rank (from 1) of the first
+                                          // and the last, 0 = none; carry: of all of them, and the NUMBERS of the first and the last
+    uint32_t sel;                         // mark: lines ending in the slice that those hits select; carry: that all hits of the frame select
+    uint32_t tail_low;                    // mark: the lowest match of the line left open at the slice's end, or 0xFFFFFFFF
+    uint32_t open_start, open_low;        // carry: where the line open at the slice's start starts; its lowest match in earlier slices, or 0xFFFFFFFF
+    uint32_t nl_base;                     // carry: 0x0A bytes of the frame in front of the slice
+    uint32_t prev_hit, next_hit;          // carry: the last hit line ending in front of the slice (0: none), the first ending behind it (0xFFFFFFFF: none)
+    uint32_t next_end, sel_excl;          // carry: the first 0x0A behind the slice, or the frame's length; selected lines of the frame in front of the slice
+};
+__global__ void zarc_lines_select_mark(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                       const int32_t *status, const uint8_t *pattern, uint32_t m, uint32_t icase, ZarcSelect q, ZarcSelSlice *slices);
+__global__ void zarc_lines_select_mark_set(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                           const int32_t *status, ZarcSetDesc sd, const uint32_t *set, uint32_t icase, ZarcSelect q, ZarcSelSlice *slices);
+__global__ void zarc_lines_select_mark_regex(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                             const int32_t *status, const ZarcRegexDfa *dfa, const uint8_t *entry, ZarcSelect q, ZarcSelSlice *slices);
+// lines[i] = the frame's hit lines, selected[i] = its selected lines
+__global__ void zarc_lines_select_carry(uint32_t n, const uint64_t *slice_prefix, const uint64_t *raw_len, ZarcSelect q, ZarcSelSlice *slices, uint32_t *lines,
+                                        uint32_t *selected);
+// rec_base[i] / deliver[i]: where frame i's records begin in rec[] and how many of its first selected lines get one
+__global__ void zarc_lines_select_emit(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                       const uint8_t *pattern, uint32_t m, uint32_t icase, ZarcSelect q, const ZarcSelSlice *slices, const uint64_t *rec_base,
+                                       const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
+__global__ void zarc_lines_select_emit_set(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                           ZarcSetDesc sd, const uint32_t *set, uint32_t icase, ZarcSelect q, const ZarcSelSlice *slices,
+                                           const uint64_t *rec_base, const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
+__global__ void zarc_lines_select_emit_regex(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                             const ZarcRegexDfa *dfa, const uint8_t *entry, ZarcSelect q, const ZarcSelSlice *slices, const uint64_t *rec_base,
+                                             const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

@@ -2186,3 +2186,4 @@ __global__ void __launch_bounds__(64) zarc_zdec_literals(const uint8_t *__restri
 #include "zdec_lines.hip"  // zarc_lines_*: the matching lines of a search, gathered from the decoded bytes
 #include "zdec_search_set.hip" // zarc_set_*, zarc_lines_*_set: a set of fixed strings in one pass
 #include "zdec_regex.hip" // zarc_regex_*, zarc_lines_*_regex: a regular expression, matched line by line
+#include "zdec_select.hip" // zarc_lines_select_*: the lines a search selects (inverted, with context), behind every matcher's bitmaps

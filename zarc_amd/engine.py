@@ -196,9 +196,13 @@ class Engine:
         return [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i])) for i in range(n)]
 
     def search_lines_device(self, d_frames, frame_off, frame_len, raw_len, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096,
-                            _fn="zarc_gpu_search_lines_batch_device"):
+                            _fn="zarc_gpu_search_lines_batch_device", invert=False, before=0, after=0):
         """search_device plus the matching lines: -> (results, records) as search_lines() gives them.  The text is gathered into a device
         buffer of rec_cap * max_line bytes and copied back from there."""
+        if invert or before or after:
+            kind = _lib.MATCH_REGEX if _fn == "zarc_gpu_search_regex_lines_batch_device" else _lib.MATCH_FIXED
+            return self.select_lines_device(d_frames, frame_off, frame_len, raw_len, kind, pattern, icase, expect, max_lines, max_line, rec_cap, invert, before,
+                                            after)[:2]
         frame_off, pfo = _u64(frame_off)
         frame_len, pfl = _u64(frame_len)
         raw_len, prl = _u64(raw_len)
@@ -247,8 +251,12 @@ class Engine:
             count.ctypes.data_as(u64p), first.ctypes.data_as(u64p), which.ctypes.data_as(u64p), hits))
         return self._set_result(n, status, dig, count, first, which), [int(v) for v in hits[:ps.count]]
 
-    def search_set_lines_device(self, d_frames, frame_off, frame_len, raw_len, patterns, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+    def search_set_lines_device(self, d_frames, frame_off, frame_len, raw_len, patterns, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096,
+                                invert=False, before=0, after=0):
         """search_lines_device for a set of patterns -> (results, records, hits) as search_set_lines() gives them."""
+        if invert or before or after:
+            return self.select_lines_device(d_frames, frame_off, frame_len, raw_len, _lib.MATCH_SET, patterns, icase, expect, max_lines, max_line, rec_cap, invert,
+                                            before, after)
         frame_off, pfo = _u64(frame_off)
         frame_len, pfl = _u64(frame_len)
         raw_len, prl = _u64(raw_len)
@@ -430,12 +438,19 @@ class Engine:
                                                    dig.ctypes.data_as(ctypes.c_void_p), status, count, first))
         return [(int(status[i]), bytes(dig[i]), int(count[i]), None if int(first[i]) == _lib.SEARCH_NONE else int(first[i])) for i in range(n)]
 
-    def search_lines(self, frames, raw_lens, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096, _fn="zarc_gpu_search_lines_batch"):
+    def search_lines(self, frames, raw_lens, pattern, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096, _fn="zarc_gpu_search_lines_batch",
+                     invert=False, before=0, after=0):
         """search() plus the lines that hold a match -> (results, records).  results[i] = (status, digest, count, first, lines): search()'s
         answer and the number of matching lines of frame i (all of them, whatever the caps).  records = [(frame, start, length, number,
         match, text_bytes)] ordered by (frame, start): per frame the first min(lines, max_lines or all) matching lines while rec_cap
         lasts; a line is a run of bytes without 0x0A, text_bytes its first min(length, max_line) bytes.  The pattern must not contain
-        0x0A.  Only the compressed frames cross to the device and only the delivered lines' bytes come back."""
+        0x0A.  Only the compressed frames cross to the device and only the delivered lines' bytes come back.
+        invert / before / after select lines as grep -v / -B / -A do (include/zarc_gpu.h, zarc_gpu_select_lines_batch): with any
+        of them set, every result tuple gains `selected` at its end, `lines` counts the hit lines, the records are the selected lines and a
+        record's match is None when its line holds no match."""
+        if invert or before or after:
+            kind = _lib.MATCH_REGEX if _fn == "zarc_gpu_search_regex_lines_batch" else _lib.MATCH_FIXED
+            return self.select_lines(frames, raw_lens, kind, pattern, icase, expect, max_lines, max_line, rec_cap, invert, before, after)[:2]
         n = len(frames)
         bufs = [bytes(f) for f in frames]
         ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
@@ -465,18 +480,20 @@ class Engine:
         needs more than 64 states with E_UNSUPPORTED."""
         return self.search(frames, raw_lens, regex, icase, expect, _fn="zarc_gpu_search_regex_batch")
 
-    def search_regex_lines(self, frames, raw_lens, regex, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+    def search_regex_lines(self, frames, raw_lens, regex, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096, invert=False, before=0, after=0):
         """search_lines() with a regular expression -> (results, records); a record's match is the lowest matching start of its line"""
-        return self.search_lines(frames, raw_lens, regex, icase, expect, max_lines, max_line, rec_cap, _fn="zarc_gpu_search_regex_lines_batch")
+        return self.search_lines(frames, raw_lens, regex, icase, expect, max_lines, max_line, rec_cap, _fn="zarc_gpu_search_regex_lines_batch",
+                                 invert=invert, before=before, after=after)
 
     def search_regex_device(self, d_frames, frame_off, frame_len, raw_len, regex, icase=False, expect=None):
         """search_device() with a regular expression (host memory)"""
         return self.search_device(d_frames, frame_off, frame_len, raw_len, regex, icase, expect, _fn="zarc_gpu_search_regex_batch_device")
 
-    def search_regex_lines_device(self, d_frames, frame_off, frame_len, raw_len, regex, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+    def search_regex_lines_device(self, d_frames, frame_off, frame_len, raw_len, regex, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096,
+                                  invert=False, before=0, after=0):
         """search_lines_device() with a regular expression (host memory)"""
         return self.search_lines_device(d_frames, frame_off, frame_len, raw_len, regex, icase, expect, max_lines, max_line, rec_cap,
-                                        _fn="zarc_gpu_search_regex_lines_batch_device")
+                                        _fn="zarc_gpu_search_regex_lines_batch_device", invert=invert, before=before, after=after)
 
     def regex_compile(self, regex, icase=False):
         """-> (states, start, accept, delta): the table the device walks for `regex`, a line's bytes from the last to the first; accept and
@@ -506,10 +523,12 @@ class Engine:
                                                        count, first, which, hits))
         return self._set_result(n, status, dig, count, first, which), [int(v) for v in hits[:ps.count]]
 
-    def search_set_lines(self, frames, raw_lens, patterns, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096):
+    def search_set_lines(self, frames, raw_lens, patterns, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096, invert=False, before=0, after=0):
         """search_lines() for a set of patterns -> (results, records, hits).  results[i] = (status, digest, count, first, which, lines) with
         search_set()'s meaning; a line matches when a matching start position of ANY pattern lies in it, and a record's match is the lowest
-        such position of its line.  No pattern may contain 0x0A.  records and the caps are search_lines()'s."""
+        such position of its line.  No pattern may contain 0x0A.  records and the caps are search_lines()'s, invert / before / after too."""
+        if invert or before or after:
+            return self.select_lines(frames, raw_lens, _lib.MATCH_SET, patterns, icase, expect, max_lines, max_line, rec_cap, invert, before, after)
         n = len(frames)
         bufs = [bytes(f) for f in frames]
         ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
@@ -533,6 +552,78 @@ class Engine:
             dig.ctypes.data_as(ctypes.c_void_p), status, count, first, which, hits, lines, rec, rec_cap, ctypes.byref(rec_used),
             text.ctypes.data_as(ctypes.c_void_p), text_cap, ctypes.byref(text_used)))
         return self._set_lines_result(n, status, dig, count, first, which, lines, rec, rec_used.value, bytes(text[:text_used.value])) + ([int(v) for v in hits[:ps.count]],)
+
+    # ---- the selected lines (zarc_gpu_select_lines_batch*): one call behind the three matchers ----
+    @staticmethod
+    def _select_result(kind, n, status, dig, count, first, which, hits, lines, selected, rec, rec_used, text):
+        none = lambda v: None if int(v) == _lib.SEARCH_NONE else int(v)
+        mid = (lambda i: (none(which[i]),)) if kind == _lib.MATCH_SET else (lambda i: ())
+        results = [(int(status[i]), bytes(dig[i]), int(count[i]), none(first[i])) + mid(i) + (int(lines[i]), int(selected[i])) for i in range(n)]
+        records = [(r.frame, r.start, r.length, r.number, none(r.match), text[r.text_off:r.text_off + r.text_len]) for r in rec[:rec_used]]
+        return results, records, ([int(v) for v in hits] if kind == _lib.MATCH_SET else None)
+
+    def select_lines(self, frames, raw_lens, kind, what, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096, invert=False, before=0, after=0):
+        """The lines a search selects -> (results, records, hits).  kind: _lib.MATCH_FIXED / MATCH_REGEX (what: bytes) or MATCH_SET (what: a
+        list of bytes).  results[i] = (status, digest, count, first[, which], lines, selected): the matcher's plain search answer, the hit
+        lines (matching lines, with invert the others) and the selected lines (hits plus `before` lines in front and `after` behind each).
+        records = the selected lines as search_lines() delivers matching lines, match None for a line without a match; hits: a set's
+        per-pattern counts, else None."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        count, first, which, lines, selected = ((ctypes.c_uint64 * n)() for _ in range(5))
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        m = _lib.MatcherDesc.of(kind, what, _lib.SEARCH_ICASE if icase else 0)
+        q = _lib.LineSelect(_lib.SELECT_INVERT if invert else 0, before, after, 0)
+        is_set = kind == _lib.MATCH_SET
+        hits = (ctypes.c_uint64 * max(len(what), 1))() if is_set else None
+        rec = (_lib.Line * max(rec_cap, 1))()
+        rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
+        text_cap = rec_cap * max_line
+        text = np.empty(max(text_cap, 1), dtype=np.uint8)
+        self._check(self.lib.zarc_gpu_select_lines_batch(
+            self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None, ctypes.byref(m), ctypes.byref(q), max_lines, max_line,
+            dig.ctypes.data_as(ctypes.c_void_p), status, count, first, which if is_set else None, hits, lines, selected, rec, rec_cap, ctypes.byref(rec_used),
+            text.ctypes.data_as(ctypes.c_void_p), text_cap, ctypes.byref(text_used)))
+        return self._select_result(kind, n, status, dig, count, first, which, hits[:len(what)] if is_set else None, lines, selected, rec, rec_used.value,
+                                   bytes(text[:text_used.value]))
+
+    def select_lines_device(self, d_frames, frame_off, frame_len, raw_len, kind, what, icase=False, expect=None, max_lines=0, max_line=4096, rec_cap=4096,
+                            invert=False, before=0, after=0):
+        """select_lines() over frames on the device; the text is gathered into a device buffer of rec_cap * max_line bytes and copied back"""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        count, first, which, lines, selected = ((ctypes.c_uint64 * max(n, 1))() for _ in range(5))
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        m = _lib.MatcherDesc.of(kind, what, _lib.SEARCH_ICASE if icase else 0)
+        q = _lib.LineSelect(_lib.SELECT_INVERT if invert else 0, before, after, 0)
+        is_set = kind == _lib.MATCH_SET
+        hits = (ctypes.c_uint64 * max(len(what), 1))() if is_set else None
+        rec = (_lib.Line * max(rec_cap, 1))()
+        rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
+        text_cap = rec_cap * max_line
+        d_text = self.malloc(max(text_cap, 1))
+        try:
+            self._check(self.lib.zarc_gpu_select_lines_batch_device(
+                self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None, ctypes.byref(m),
+                ctypes.byref(q), max_lines, max_line, dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), count, first,
+                which if is_set else None, hits, lines, selected, rec, rec_cap, ctypes.byref(rec_used), ctypes.c_void_p(d_text), text_cap, ctypes.byref(text_used)))
+            text = bytes(self.d2h(d_text, text_used.value)) if text_used.value else b""
+        finally:
+            self.free(d_text)
+        return self._select_result(kind, n, status, dig, count, first, which, hits[:len(what)] if is_set else None, lines, selected, rec, rec_used.value, text)
 
     def repack(self, frames, raw_lens, expect=None):
         """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with

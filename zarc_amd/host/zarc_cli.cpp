@@ -196,7 +196,7 @@ int usage()
                          "         --keep-smaller copies a frame unchanged when its new form is not smaller.  A frame that is not good ends the run with\n"
                          "         exit status 1 and nothing is left at PATH\n"
                          "       zarc grep [-i] [-l] [-b] [--hex] [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
-                         "                 [--lines] [-n] [-c] [-a] [-m NUM] [--max-line BYTES] [--batch-lines N] PATTERN ARCHIVE\n"
+                         "                 [--lines] [-n] [-c] [-a] [-m NUM] [--max-line BYTES] [--batch-lines N] [-v] [-A NUM] [-B NUM] [-C NUM] PATTERN ARCHIVE\n"
                          "       zarc grep ... (-e PATTERN | -f FILE)... [--tally] ARCHIVE\n"
                          "       zarc grep -E ... (PATTERN | (-e PATTERN | -f FILE)...) ARCHIVE\n"
                          "         searches the content of the files for PATTERN on the device, each distinct frame once, and writes nothing.  PATTERN is a\n"
@@ -209,6 +209,11 @@ int usage()
                          "         `Binary file PATH matches` unless -a is given.  A line prints its first --max-line bytes (default 4096, 1 to 65536).\n"
                          "         --batch-lines N (default 1048576) is the number of lines one device call can bring back; what did not fit is searched again.\n"
                          "         PATTERN must not contain a newline in lines mode\n"
+                         "         -v selects the lines WITHOUT a match, -A NUM / -B NUM / -C NUM add NUM lines behind / in front of / around every selected\n"
+                         "         line, chosen on the device; each selects lines mode (inside grep, -v is not the global verbosity flag).  Output is grep's:\n"
+                         "         context lines carry `-` in place of every `:`, a line `--` stands between groups that are not adjacent; -c, -l and the exit\n"
+                         "         status follow the selected (hit) lines; with -m NUM a file stops behind the trailing context of its NUM-th hit line.  They\n"
+                         "         go with one PATTERN, -e / -f and -E, not with --tally\n"
                          "         -e PATTERN (any number of times) and -f FILE (one pattern per line; a CR stays part of it, an empty line is an error) give a\n"
                          "         SET of up to 1024 patterns that is searched in one pass; ARCHIVE is then the only other argument and --hex applies to every\n"
                          "         pattern.  Patterns that are equal (after -i) are searched once.  A position at which several patterns match counts once, a\n"
@@ -762,6 +767,16 @@ int cmd_grep(const std::vector<std::string> &a)
     std::vector<std::string> typed; // -e / -f: the patterns of a set, as given
     bool use_set = false, tally = false;
     bool ere = false; // -E: PATTERN is a regular expression (zarc_gpu_search_regex_batch*)
+    zarc::LineSelect sel; // -v, -A, -B, -C: the selected lines (zarc_gpu_select_lines_batch); any of them selects lines mode
+    auto context = [&](char which, const std::string &num) { // -A NUM, -B NUM, -C NUM; false: not a number
+        if (num.empty() || num.find_first_not_of("0123456789") != std::string::npos) return false;
+        const unsigned long long v = std::strtoull(num.c_str(), nullptr, 10);
+        const uint32_t n = v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v;
+        if (which != 'B') sel.after = n;
+        if (which != 'A') sel.before = n;
+        lines_mode = true;
+        return true;
+    };
     for (size_t i = 0; i < a.size(); i++) {
         if (options && a[i] == "--filter" && i + 1 < a.size()) filters.emplace_back(a[++i]);
         else if (options && a[i] == "-e" && i + 1 < a.size()) { typed.push_back(a[++i]); use_set = true; }
@@ -798,6 +813,13 @@ int cmd_grep(const std::vector<std::string> &a)
                 else if (a[i][k] == 'n') numbers = lines_mode = true;
                 else if (a[i][k] == 'c') count_lines = lines_mode = true;
                 else if (a[i][k] == 'a') as_text = lines_mode = true;
+                else if (a[i][k] == 'v') sel.invert = lines_mode = true;
+                else if (a[i][k] == 'A' || a[i][k] == 'B' || a[i][k] == 'C') { // the number follows in this argument or is the next one
+                    const std::string num = k + 1 < a[i].size() ? a[i].substr(k + 1) : (i + 1 < a.size() ? a[i + 1] : std::string());
+                    if (!context(a[i][k], num)) return usage();
+                    if (k + 1 >= a[i].size()) i++;
+                    break;
+                }
                 else return usage();
             }
         } else if (options && a[i].size() >= 2 && a[i][0] == '-') return usage();
@@ -812,6 +834,7 @@ int cmd_grep(const std::vector<std::string> &a)
         if (typed.empty()) { std::fprintf(stderr, "Error: no pattern\n"); return 2; }
     } else typed.push_back(pattern);
     if (!have_pattern || input.empty() || gpus < 1 || gpus > 64) return usage();
+    if (sel.active() && tally) return usage(); // the tally counts positions: there is no line to select
     if (ere) { // several expressions are one alternation, as in grep; a bad one is refused here, before the archive is opened
         if (hex || tally) return usage();
         std::string joined;
@@ -888,7 +911,15 @@ int cmd_grep(const std::vector<std::string> &a)
             // -c and -l need no line: a counting call.  Otherwise one call brings back at most --batch-lines lines; frames behind the one
             // at which they ran out are searched again in a following call, and a frame that is first in its call and still has more
             // than fit prints what it got and says so.
+            // With -v / -A / -B / -C the lines are the selected ones (zarc_gpu_select_lines_batch).  -m NUM then follows GNU grep: a file stops
+            // after its NUM-th hit line, that line's trailing context is still printed, as context even where it matches -- so the device is
+            // asked for NUM * (before + after + 1) lines, which hold all of that, and the rest is trimmed here by line number.
             const bool need_lines = !count_lines && !names_only;
+            uint64_t per_frame = (uint64_t)max_per_file;
+            if (sel.active() && max_per_file) {
+                const uint64_t group = (uint64_t)sel.before + sel.after + 1;
+                per_frame = (uint64_t)max_per_file > UINT64_MAX / group ? 0 : (uint64_t)max_per_file * group; // (saturates to "no limit")
+            }
             std::map<zarc::Digest, zarc::FrameReader::Result> done;
             const size_t BATCH = (size_t)1 << 30;
             size_t at = 0;
@@ -899,18 +930,20 @@ int cmd_grep(const std::vector<std::string> &a)
                 for (size_t batch_bytes = 0; at + batch.size() < todo.size() && batch_bytes < BATCH; batch_bytes += (size_t)rd.frames().at(batch.back()).uncompressed)
                     batch.push_back(todo[at + batch.size()]);
                 std::vector<zarc::FrameReader::Result> res =
-                    use_set ? rd.search_set_lines(batch, set, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0)
-                    : ere   ? rd.search_regex_lines(batch, pattern, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0)
-                            : rd.search_lines(batch, pattern, icase, (uint64_t)max_per_file, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0);
+                    use_set ? rd.search_set_lines(batch, set, icase, per_frame, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0, nullptr, sel)
+                    : ere   ? rd.search_regex_lines(batch, pattern, icase, per_frame, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0, sel)
+                            : rd.search_lines(batch, pattern, icase, per_frame, (uint64_t)max_line, need_lines ? (size_t)batch_lines : 0, sel);
                 LOGF(3, "search_lines", "frames=%zu", batch.size());
                 size_t taken = batch.size();
                 for (size_t k = 0; k < batch.size(); k++) {
-                    const uint64_t want = need_lines ? (max_per_file ? std::min<uint64_t>(res[k].lines, (uint64_t)max_per_file) : res[k].lines) : 0;
+                    const uint64_t want = need_lines ? (per_frame ? std::min<uint64_t>(res[k].selected, per_frame) : res[k].selected) : 0;
                     if (k > 0 && res[k].line_records.size() < want) { taken = k; break; } // the call's records ran out here: this frame and the rest again
                     done[batch[k]] = std::move(res[k]);
                 }
                 at += taken;
             }
+            const bool groups = sel.before || sel.after; // grep prints `--` between groups of lines that are not adjacent
+            bool printed = false;
             for (size_t i = 0; i < rd.files().size(); i++) {
                 const zarc::File &f = rd.files()[i];
                 if (!f.is_normal() || !passes(filters, to_path(f.name)) || !done.count(*f.digest)) continue;
@@ -931,17 +964,26 @@ int cmd_grep(const std::vector<std::string> &a)
                 bool binary = false;
                 if (!as_text) for (const auto &l : r.line_records) binary = binary || std::memchr(l.text.data(), 0, l.text.size()) != nullptr;
                 if (binary) { std::printf("Binary file %s matches\n", path.c_str()); continue; }
+                uint64_t hits_seen = 0, stop_behind = UINT64_MAX, last_number = UINT64_MAX - 1; // (a file's first line opens a new group)
                 for (const auto &l : r.line_records) {
-                    std::printf("%s:", path.c_str());
-                    if (numbers) std::printf("%llu:", (unsigned long long)l.number);
-                    if (with_offset) std::printf("%llu:", (unsigned long long)l.start);
+                    if (l.number > stop_behind) break; // -m with context: behind the last hit line's trailing context
+                    const bool stopped = stop_behind != UINT64_MAX;
+                    const bool hit = !stopped && (l.match != ZARC_GPU_SEARCH_NONE) != sel.invert;
+                    if (groups && printed && l.number != last_number + 1) std::printf("--\n");
+                    const char sep = hit ? ':' : '-';
+                    std::printf("%s%c", path.c_str(), sep);
+                    if (numbers) std::printf("%llu%c", (unsigned long long)l.number, sep);
+                    if (with_offset) std::printf("%llu%c", (unsigned long long)l.start, sep);
                     std::fwrite(l.text.data(), 1, l.text.size(), stdout);
                     std::fputc('\n', stdout);
+                    printed = true; last_number = l.number;
                     if (l.length > l.text.size())
                         std::fprintf(stderr, "WARN line cut path=%s line=%llu length=%llu\n", path.c_str(), (unsigned long long)l.number, (unsigned long long)l.length);
+                    if (hit && sel.active() && max_per_file && ++hits_seen == (uint64_t)max_per_file) stop_behind = l.number + sel.after;
                 }
-                if (r.line_records.size() < shown)
-                    std::fprintf(stderr, "WARN path=%s: %llu more matching lines not shown\n", path.c_str(), (unsigned long long)(shown - r.line_records.size()));
+                const uint64_t expected = sel.active() ? (per_frame ? std::min<uint64_t>(r.selected, per_frame) : r.selected) : shown;
+                if (r.line_records.size() < expected)
+                    std::fprintf(stderr, "WARN path=%s: %llu more matching lines not shown\n", path.c_str(), (unsigned long long)(expected - r.line_records.size()));
             }
             std::fprintf(stderr, "searched %llu files (%zu frames, %llu bytes), %llu match, %llu failed\n", n_files, order.size(), bytes, matched, failed);
             return failed ? 2 : (matched ? 0 : 1);

@@ -447,9 +447,10 @@ class ArchiveReader {
         return reader_.search_content_frames(data_, len_, wanted, pattern, icase);
     }
     // search_frames plus the matching lines of every frame (FrameReader::lines_content_frames): per digest, in order, `lines` and the
-    // records the delivery rule gives it; only the delivered lines' bytes come back
+    // records the delivery rule gives it; only the delivered lines' bytes come back.  sel: the selected lines in place of the matching ones
+    // (grep's -v, -A, -B, -C), for this call and its two siblings below
     std::vector<FrameReader::Result> search_lines(const std::vector<Digest> &digests, const std::string &pattern, bool icase = false, uint64_t max_lines = 0,
-                                                  uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20)
+                                                  uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20, const LineSelect &sel = LineSelect())
     {
         std::vector<Frame> wanted;
         for (const Digest &d : digests) {
@@ -457,7 +458,7 @@ class ArchiveReader {
             if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
             wanted.push_back(it->second);
         }
-        return reader_.lines_content_frames(data_, len_, wanted, pattern, icase, max_lines, max_line, rec_cap);
+        return reader_.lines_content_frames(data_, len_, wanted, pattern, icase, max_lines, max_line, rec_cap, sel);
     }
     // search_frames for a set of fixed byte strings in one pass (FrameReader::search_set_content_frames): count, first and which of the
     // union per digest, in order; hits (may be null) receives the per-pattern sums over these frames
@@ -475,7 +476,7 @@ class ArchiveReader {
     // ... and search_lines for a set (FrameReader::lines_set_content_frames)
     std::vector<FrameReader::Result> search_set_lines(const std::vector<Digest> &digests, const std::vector<std::string> &patterns, bool icase = false,
                                                       uint64_t max_lines = 0, uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20,
-                                                      std::vector<uint64_t> *hits = nullptr)
+                                                      std::vector<uint64_t> *hits = nullptr, const LineSelect &sel = LineSelect())
     {
         std::vector<Frame> wanted;
         for (const Digest &d : digests) {
@@ -483,7 +484,7 @@ class ArchiveReader {
             if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
             wanted.push_back(it->second);
         }
-        return reader_.lines_set_content_frames(data_, len_, wanted, patterns, icase, max_lines, max_line, rec_cap, hits);
+        return reader_.lines_set_content_frames(data_, len_, wanted, patterns, icase, max_lines, max_line, rec_cap, hits, sel);
     }
     // search_frames with a regular expression in place of the fixed string (FrameReader::search_regex_content_frames): matching is per line
     std::vector<FrameReader::Result> search_regex(const std::vector<Digest> &digests, const std::string &regex, bool icase = false)
@@ -498,7 +499,7 @@ class ArchiveReader {
     }
     // ... and search_lines with one (FrameReader::lines_regex_content_frames)
     std::vector<FrameReader::Result> search_regex_lines(const std::vector<Digest> &digests, const std::string &regex, bool icase = false, uint64_t max_lines = 0,
-                                                        uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20)
+                                                        uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20, const LineSelect &sel = LineSelect())
     {
         std::vector<Frame> wanted;
         for (const Digest &d : digests) {
@@ -506,7 +507,7 @@ class ArchiveReader {
             if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
             wanted.push_back(it->second);
         }
-        return reader_.lines_regex_content_frames(data_, len_, wanted, regex, icase, max_lines, max_line, rec_cap);
+        return reader_.lines_regex_content_frames(data_, len_, wanted, regex, icase, max_lines, max_line, rec_cap, sel);
     }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()

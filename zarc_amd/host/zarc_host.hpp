@@ -358,6 +358,14 @@ class Encoder {
     uint64_t offset_ = 0;
 };
 
+// Which lines a lines call delivers (zarc_gpu_line_select): the hit lines -- the matching lines, with `invert` the others -- and `before`
+// lines in front of and `after` lines behind each.  The default selects the matching lines: the call is then the plain lines call.
+struct LineSelect {
+    bool invert = false;
+    uint32_t before = 0, after = 0;
+    bool active() const { return invert || before || after; }
+};
+
 // Decoder::read_content_frame + FrameIterator for a batch of frames of one archive image held in memory.
 // The reference's read side is a serial loop over frames that each get a fresh reader and DCtx (zarc-cli/src/unpack.rs:62-88,
 // decode/zstd_iterator.rs:28-29): frames are as independent on the way out as on the way in.  A FrameReader constructed with G
@@ -377,7 +385,8 @@ class FrameReader {
         // lines_content_frames: the frame's matching lines, all of them counted, and the records of those that were delivered (they own their bytes)
         struct Line { uint64_t start, length, number, match; std::vector<uint8_t> text; }; // zarc_gpu_line; text: the line's first min(length, max_line) bytes
         uint64_t lines = 0;
-        std::vector<Line> line_records;
+        uint64_t selected = 0;           // with a LineSelect: the lines it selects (lines: the hit lines); without one: lines
+        std::vector<Line> line_records;  // a selected line without a match: match == ZARC_GPU_SEARCH_NONE
     };
     explicit FrameReader(int device = 0) : FrameReader(std::vector<int>{device}) {}
     explicit FrameReader(const std::vector<int> &devices)
@@ -415,14 +424,17 @@ class FrameReader {
     // records the delivery rule gives it -- frames in the caller's order, per frame the first min(lines, max_lines or all, what rec_cap
     // leaves) matching lines.  Every handle runs its share with the caller's caps, the shares are merged in the caller's order and the rule
     // is applied once more on the merged list: the results are identical for every number of handles.  Only the delivered lines' bytes
-    // come back.  The pattern must not contain 0x0A.
+    // come back.  The pattern must not contain 0x0A.  With an active `sel` the call is zarc_gpu_select_lines_batch: the records are the
+    // selected lines, `lines` counts the hit lines and `selected` the selected ones, dealt and merged in the same way.
     std::vector<Result> lines_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const std::string &pattern,
-                                             bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20)
+                                             bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20,
+                                             const LineSelect &sel = LineSelect())
     {
         if (pattern.empty() || pattern.size() > ZARC_GPU_SEARCH_MAX_PATTERN) throw Error(ZARC_GPU_E_PARAM, "the pattern has 1 to 256 bytes");
         if (pattern.find('\n') != std::string::npos) throw Error(ZARC_GPU_E_PARAM, "the pattern must not contain a newline");
         if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) throw Error(ZARC_GPU_E_PARAM, "max_line is 1 to 65536");
-        const Search s{&pattern, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, true, max_lines, max_line, rec_cap};
+        Search s{&pattern, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, true, max_lines, max_line, rec_cap};
+        if (sel.active()) s.select = &sel;
         std::vector<Result> out = run_frames(archive, archive_len, wanted, false, &s);
         size_t left = rec_cap;
         for (Result &r : out) { // the delivery rule over the merged list (a handle saw fewer frames in front of this one: it delivered no less)
@@ -449,12 +461,13 @@ class FrameReader {
     // record's `match` is the lowest such position.  No pattern may contain 0x0A.
     std::vector<Result> lines_set_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted,
                                                  const std::vector<std::string> &patterns, bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096,
-                                                 size_t rec_cap = (size_t)1 << 20, std::vector<uint64_t> *hits = nullptr)
+                                                 size_t rec_cap = (size_t)1 << 20, std::vector<uint64_t> *hits = nullptr, const LineSelect &sel = LineSelect())
     {
         check_set(patterns, true);
         if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) throw Error(ZARC_GPU_E_PARAM, "max_line is 1 to 65536");
         Search s{nullptr, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, true, max_lines, max_line, rec_cap};
         s.set = &patterns; s.hits = hits;
+        if (sel.active()) s.select = &sel;
         if (hits) hits->assign(patterns.size(), 0);
         std::vector<Result> out = run_frames(archive, archive_len, wanted, false, &s);
         size_t left = rec_cap;
@@ -478,12 +491,14 @@ class FrameReader {
     }
     // ... and lines_content_frames with one (zarc_gpu_search_regex_lines_batch)
     std::vector<Result> lines_regex_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const std::string &regex,
-                                                   bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20)
+                                                   bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096, size_t rec_cap = (size_t)1 << 20,
+                                                   const LineSelect &sel = LineSelect())
     {
         check_regex(regex, icase);
         if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) throw Error(ZARC_GPU_E_PARAM, "max_line is 1 to 65536");
         Search s{&regex, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, true, max_lines, max_line, rec_cap};
         s.regex = true;
+        if (sel.active()) s.select = &sel;
         std::vector<Result> out = run_frames(archive, archive_len, wanted, false, &s);
         size_t left = rec_cap;
         for (Result &r : out) { // the delivery rule over the merged list, as in lines_content_frames
@@ -499,6 +514,7 @@ class FrameReader {
         bool regex = false;                            // `pattern` is a regular expression
         const std::vector<std::string> *set = nullptr; // a set of patterns in place of the one
         std::vector<uint64_t> *hits = nullptr;         // ... and its per-pattern sums over all handles
+        const LineSelect *select = nullptr;            // lines: the selected lines in place of the matching ones
     };
     static void check_regex(const std::string &regex, bool icase)
     {
@@ -555,19 +571,31 @@ class FrameReader {
             }
             // lines: no frame holds more matching lines than it has room for matches, so a share's records never need more than this -- and
             // neither does its text buffer, which the call wants rec_cap * max_line bytes large (never touched beyond what is delivered)
-            std::vector<uint64_t> nlines;
+            std::vector<uint64_t> nlines, nselected;
             std::vector<zarc_gpu_line> rec;
             std::unique_ptr<uint8_t, void (*)(void *)> text(nullptr, std::free);
             size_t rec_cap = 0, rec_used = 0, text_used = 0;
             if (search && search->lines) {
                 uint64_t room = 0;
-                for (size_t j = 0; j < m; j++) room += ul[j] / shortest + 1;
+                for (size_t j = 0; j < m; j++) room += (search->select ? ul[j] : ul[j] / shortest) + 1; // (selected: no frame has more lines than bytes)
                 rec_cap = (size_t)std::min<uint64_t>(search->rec_cap, room);
-                nlines.resize(m); rec.resize(rec_cap);
+                nlines.resize(m); nselected.resize(m); rec.resize(rec_cap);
                 text.reset((uint8_t *)std::malloc(std::max<size_t>(1, rec_cap * (size_t)search->max_line)));
                 if (!text) { rc[d] = ZARC_GPU_E_NOMEM; return; }
             }
-            rc[d] = search && search->set && search->lines
+            zarc_gpu_matcher mt{ZARC_GPU_MATCH_FIXED, search ? search->flags : 0u, nullptr, 0, nullptr};
+            zarc_gpu_line_select ls{0, 0, 0, 0};
+            if (search && search->select) {
+                if (search->set) { mt.kind = ZARC_GPU_MATCH_SET; mt.set = &pset; }
+                else { mt.kind = search->regex ? ZARC_GPU_MATCH_REGEX : ZARC_GPU_MATCH_FIXED; mt.text = search->pattern->data(); mt.text_len = search->pattern->size(); }
+                ls = zarc_gpu_line_select{search->select->invert ? (uint32_t)ZARC_GPU_SELECT_INVERT : 0u, search->select->before, search->select->after, 0};
+            }
+            rc[d] = search && search->lines && search->select
+                        ? zarc_gpu_select_lines_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), &mt, &ls,
+                                                      search->max_lines, search->max_line, (uint8_t(*)[32])got.data(), status.data(), count.data(), first.data(),
+                                                      search->set ? which.data() : nullptr, search->set ? share_hits[d].data() : nullptr, nlines.data(),
+                                                      nselected.data(), rec.data(), rec_cap, &rec_used, text.get(), rec_cap * (size_t)search->max_line, &text_used)
+                    : search && search->set && search->lines
                         ? zarc_gpu_search_set_lines_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), &pset,
                                                           search->flags, search->max_lines, search->max_line, (uint8_t(*)[32])got.data(), status.data(), count.data(),
                                                           first.data(), which.data(), share_hits[d].data(), nlines.data(), rec.data(), rec_cap, &rec_used, text.get(),
@@ -606,7 +634,7 @@ class FrameReader {
                 else r.data.clear();
                 if (search) { r.count = count[j]; if (first[j] != ZARC_GPU_SEARCH_NONE) r.first = first[j]; }
                 if (search && search->set && which[j] != ZARC_GPU_SEARCH_NONE) r.which = which[j];
-                if (search && search->lines) r.lines = nlines[j];
+                if (search && search->lines) { r.lines = nlines[j]; r.selected = search->select ? nselected[j] : nlines[j]; }
             }
             for (size_t k = 0; k < rec_used; k++) {
                 const zarc_gpu_line &l = rec[k];
