@@ -145,6 +145,16 @@ __device__ __forceinline__ void store_streaming(uint64_t *p, uint64_t v)
 #endif
 }
 
+// a * b + c for a, b < 2^24 (v_mad_u32_u24: full rate, where a 32-bit multiply runs at a quarter)
+__device__ __forceinline__ uint32_t mad24(uint32_t a, uint32_t b, uint32_t c)
+{
+#ifdef ZARC_HIPEMU
+    return (a & 0xFFFFFFu) * (b & 0xFFFFFFu) + c;
+#else
+    return __umul24(a, b) + c;
+#endif
+}
+
 __device__ __forceinline__ uint32_t rotr32(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
 __device__ __forceinline__ uint64_t rotl64(uint64_t x, int n) { return (x << n) | (x >> (64 - n)); }
 __device__ __forceinline__ int hb32(uint32_t v) { return 31 - __clz((int)v); }          // floor(log2 v), v > 0

@@ -83,7 +83,7 @@ template <int TAB_LOG, bool NEAR16> struct MatchLds {
     static constexpr int TAB_WORDS = NEAR16 ? (1 << TAB_LOG) / 2 : 2 << TAB_LOG;
     uint32_t tab[TAB_WORDS + (NEAR16 ? 1 : 0)]; // NEAR16: one more word = slot 2^TAB_LOG, where positions without a hash look up and store (no branch in the chain)
     uint32_t a0[TILE], a1[TILE]; // S1: hashes -> S2: candidates (pos+1) -> S3: a0 = own match (match_pack) -> S4: a1 = final match (deep finder)
-    uint32_t ex[TILE];            // S4: best backward offer per position; S6: first position outside its chunk reached from each position
+    uint32_t ex[TILE];            // S4: best backward offer per position (0: none; the source's word G, not yet the key: zge_parse_round.h); S6: first position outside its chunk reached from each position
                                   // (level-3 and fast finder: those exits go to a1 and ex keeps the offers to the end of the tile, see LAZY_BY_LANE)
     uint32_t tb[2][(TB_BYTES + 3) / 4]; // the window of a tile lives in buffer (tile / TILE) & 1: the current tile's and the next one's
     uint32_t wcnt[CHUNKS];       // S6: selected matches << 16 | literals of each chunk
@@ -237,6 +237,11 @@ __device__ __forceinline__ void zge_match_body(MatchLds<TAB_LOG, NEAR16> &L, con
     // The chunk exits of S6 then live in a1[] -- free with one near table once the thread's own far insert has read its word (program
     // order), and until the next tile's S1 behind two barriers -- because ex[] must keep the offers for a wave that is still in adoption.
     constexpr bool LAZY_BY_LANE = NEAR16 && !LAZY2 && !REP_PASS;
+    // S4's offers (zge_parse_round.h): a source posts G = (score + OFFER_BIAS) << 6 | 63, plus OFFER_C times its tile position.  A
+    // score stays below 6 * (LONG_CAP + 48), a tile position below 1024: G < 2^20, and both products fit the 24-bit multiplier.
+    constexpr uint32_t OFFER_C = 64u * (uint32_t)LITC - 1u;
+    constexpr int32_t OFFER_BIAS = 64;
+    static_assert(((uint64_t)(LITC * (LONG_CAP + 48) + OFFER_BIAS) << 6) + 63 + (uint64_t)OFFER_C * (TILE - 1) < (1u << 20), "an offer is a 20-bit word");
     uint32_t *const Lexit = LAZY_BY_LANE ? L.a1 : L.ex;
     uint32_t *const Ltl = L.tab, *const Lts = L.tab + (NEAR16 ? 0 : (1 << TAB_LOG)); // long / short table (not NEAR16)
     typedef uint16_t __attribute__((may_alias)) u16a;

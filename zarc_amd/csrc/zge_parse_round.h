@@ -6,8 +6,12 @@
 // Uses the locals of the tile loop; writes fo / fw (final match per position), msel / mlit (the path's matches / literals per chunk).
 // Workgroup barriers of one pass: S4, [deep finder: adoption -> S5,] S6a -> S6b, S6 -> S7.
             // ---- S4: backward propagation.  A position whose match extends b bytes backwards offers it to the b
-            // positions before it (ds_max of score << 6 | 63-k: best score wins, then the nearest source); every position
-            // then adopts the best offer if it beats its own match.  Same result as scanning the 8 following positions.
+            // positions before it; every position then adopts the best offer if it beats its own match: best score wins, then
+            // the nearest source.  Same result as scanning the 8 following positions.  The offer of source s (own score base) to
+            // target t = s - k is the key (base + LITC k + OFFER_BIAS) << 6 | 63 - k = G(s) - OFFER_C t with
+            // G(s) = (base + OFFER_BIAS) << 6 | 63, plus OFFER_C s, and OFFER_C = 64 LITC - 1: what depends on the distance is
+            // the same for every offer that reaches t, so the source posts the ONE word G(s) to all its targets (ds_max) and
+            // the target takes OFFER_C t off the winner once.  The bias keeps the unsigned order right whatever base is.
 #pragma unroll
             for (int u = 0; u < PER; u++) {
                 const uint32_t idx = ZGE_IDX(u);
@@ -18,15 +22,11 @@
                     // bookkeeping -- compare, mask, two branches per trip -- was twice the work of the offers themselves, 9 % of the kernel
                     const int32_t base = score_of(P, len, mo[u], rep); // the score is linear in the length: + lit_cost per byte
                     const uint32_t lim = back < idx ? back : idx;
+                    const uint32_t g = zd::mad24(OFFER_C, idx, ((uint32_t)(base + OFFER_BIAS) << 6) + 63u); // G(idx): one word for every target
 #pragma unroll
-                    for (uint32_t k = 1; k <= (uint32_t)F_BACK_CAP; k++) {
-                        const int32_t sc = base + LITC * (int32_t)k;
-                        if (k <= lim && sc > 0) atomicMax(&L.ex[idx - k], ((uint32_t)sc << 6) | (63u - k));
-                    }
-                    for (uint32_t k = (uint32_t)F_BACK_CAP + 1; k <= lim; k++) { // far candidates reach further back
-                        const int32_t sc = base + LITC * (int32_t)k;
-                        if (sc > 0) atomicMax(&L.ex[idx - k], ((uint32_t)sc << 6) | (63u - k));
-                    }
+                    for (uint32_t k = 1; k <= (uint32_t)F_BACK_CAP; k++)
+                        if (k <= lim) atomicMax(&L.ex[idx - k], g);
+                    for (uint32_t k = (uint32_t)F_BACK_CAP + 1; k <= lim; k++) atomicMax(&L.ex[idx - k], g); // far candidates reach further back
                 }
             }
 #if ZGE_FIRST
@@ -99,13 +99,15 @@
                 uint32_t blen_ = mw[u] & 0xFFFF, boff = mo[u];
                 bool brep = (mw[u] >> 24) & 1;
                 int32_t fs = blen_ ? score_of(P, blen_, boff, brep) : 0;
-                if (offer && (int32_t)(offer >> 6) > fs) {
-                    const uint32_t k = 63u - (offer & 63u);
+                const uint32_t key = offer - zd::mad24(OFFER_C, idx, 0); // (score + bias) << 6 | 63 - k of the winning source (offer != 0)
+                const int32_t osc = (int32_t)(key >> 6) - OFFER_BIAS;
+                if (offer && osc > fs) {
+                    const uint32_t k = 63u - (key & 63u);
                     const uint32_t nm = L.a0[idx + k];
                     boff = match_off(nm);
                     blen_ = match_len(nm) + k;
                     brep = match_rep(nm);
-                    fs = (int32_t)(offer >> 6);
+                    fs = osc;
                 }
                 fo[u] = boff;
                 fw[u] = blen_ | ((brep ? 1u : 0u) << 24);
@@ -125,7 +127,8 @@
                     const uint32_t offer = L.ex[e], em = L.a0[e];
                     const uint32_t el = match_len(em);
                     edge = el ? score_of(P, el, match_off(em), match_rep(em)) : 0;
-                    if (offer && (int32_t)(offer >> 6) > edge) edge = (int32_t)(offer >> 6);
+                    const int32_t osc = (int32_t)((offer - OFFER_C * e) >> 6) - OFFER_BIAS; // (OFFER_C e is uniform: a scalar product)
+                    if (offer && osc > edge) edge = osc;
                 }
                 const int32_t first1 = (int32_t)zd::readlane((uint32_t)fsc[1], 0);
                 const int32_t above0 = (int32_t)zd::shfl_down1((uint32_t)fsc[0]), above1 = (int32_t)zd::shfl_down1((uint32_t)fsc[1]); // (whole wave)
