@@ -47,7 +47,8 @@ extern "C" {
                                   zarc_gpu_last_kernel_ms of an older library answers < 0 for the new id, as for any id it does not know), and
                                   zarc_gpu_search_lines_batch* with ZARC_GPU_T_LINES after those (ZARC_GPU_T_COUNT grew from 11 to 12), then
                                   zarc_gpu_search_set_*, and zarc_gpu_regex_compile with zarc_gpu_search_regex_* (new symbols; ZARC_GPU_T_COUNT stays 12), then
-                                  zarc_gpu_select_lines_batch* (new symbols and types; nothing existing changes) */
+                                  zarc_gpu_select_lines_batch* (new symbols and types; nothing existing changes), then zarc_gpu_search_matches_batch* with
+                                  zarc_gpu_regex_compile_ends and zarc_gpu_match (the same: new symbols and one new type) */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -515,6 +516,85 @@ int zarc_gpu_select_lines_batch_device(zarc_gpu_t *h, size_t n, const void *d_fr
                                        uint64_t *lines, uint64_t *selected, zarc_gpu_line *rec /* HOST array */, size_t rec_cap, size_t *rec_used,
                                        void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
 
+/* ---- search, only the matches: every match of a matching line, cut out on the device ------------------------------------------------------- */
+/* What `grep -o` prints: not the lines that hold a match but the matches themselves, each with its start, its length and its bytes.  Only
+ * the matched bytes leave the device.  A LINE and a MATCHING START POSITION are what the lines calls define, per matcher kind (FIXED:
+ * zarc_gpu_search_lines_batch, SET: zarc_gpu_search_set_lines_batch, REGEX: zarc_gpu_search_regex_batch).  Let M be the set of matching
+ * start positions of one line [ls, le).
+ *   - The END of the match at p in M is E(p):
+ *       FIXED  p + pattern_len.
+ *       SET    p + max len[k] over the patterns k that match at p, under the per-pattern frame-end rule.  `which` is the lowest k among the
+ *              patterns of that length that match at p.
+ *       REGEX  the largest j with p < j <= le and content[p .. j) in L(R).  `^` holds only if p == ls, `$` only if j == le.  This is POSIX
+ *              leftmost-longest.
+ *   - The MATCHES of the line are what `grep -o` prints: c = ls; repeat: p = min{s in M : s >= c}; if there is none, stop; the match is
+ *     (p, E(p) - p); then c = E(p).  Matches never overlap.  A regex cannot match without consuming a byte (refused, see
+ *     zarc_gpu_regex_compile), so the loop advances.  The first match of a line starts at the line record's `match`.
+ *   - The calls take a zarc_gpu_matcher (FIXED, SET or REGEX, with ZARC_GPU_SEARCH_ICASE as that kind takes it) and no zarc_gpu_line_select.
+ *   - status, digest, count, first (SET: which, hits; both may be NULL, non-NULL with another kind is ZARC_GPU_E_PARAM) and lines[i] are
+ *     EXACTLY the matcher's own lines call's.
+ *   - Lines.  Frame i takes part with its first d_i = min(lines[i], max_lines (0 = no limit), line_cap - sum of d_j, j < i) matching lines:
+ *     the lines calls' delivery rule with line_cap in rec_cap's place.  Line records are internal and never leave the device.
+ *   - matches[i] = the number of matches in those d_i lines, whatever rec_cap.
+ *   - Records.  Frame i delivers its first e_i = min(matches[i], rec_cap - sum of e_j, j < i) matches in ascending `start`; a cut may fall
+ *     inside a line.  Records are ordered by (frame, start).  *rec_used = the sum of e_i.
+ *   - Text.  text_len = min(length, max_line), the match's first bytes; text_off is the running sum in record order, *text_used the whole
+ *     sum.  text_cap < rec_cap * max_line (or a product that overflows): ZARC_GPU_E_DSTSIZE.
+ *   - line_cap == 0 or rec_cap == 0 is a counting call: rec and text may be NULL, both *_used are 0; matches[i] is what the rules above
+ *     give, so 0 when line_cap == 0.
+ *   - Checks: the matcher's own lines call's, in its order (with the matches call's rec_cap in the text_cap rule); for a REGEX the forward
+ *     table is compiled right behind the backward one and refused as zarc_gpu_regex_compile_ends refuses it; then, as ZARC_GPU_E_PARAM, a
+ *     missing matches / rec_used / text_used, or a NULL rec or text with both caps > 0.  A missing matcher and an unknown kind are
+ *     ZARC_GPU_E_PARAM as well.  n == 0: ZARC_GPU_OK (the matcher is validated all the same), both *_used 0.
+ *   - Host form: the frames go up and exactly *text_used bytes of content come back (zarc_gpu_last_copy_bytes: H2D = sum of frame_len,
+ *     D2H = *text_used).  Device form: `rec` and every per-frame array are host arrays, d_text is device memory; the counters report 0.
+ *   - Results are the same for every ZARC_GPU_PX_SCRATCH_MB, every ZARC_GPU_PX_STAGE_CHUNK, both forms and every number of handles: the
+ *     remainders of line_cap, rec_cap and the text offset are carried from part to part.
+ *   - zarc_gpu_last_kernel_ms: ZARC_GPU_T_LINES covers zarc_matches_* as well.
+ *   - Cost: everything up to the line records is the matcher's lines call.  Behind it one lane walks one delivered line: a frame that is one
+ *     1 MiB line is walked serially, at roughly 50 cycles per dependent LDS lookup (a regex: the line's length, plus for every match the
+ *     bytes from its start to where the forward table dies or the line ends); ordinary text is hundreds of lines per workgroup in
+ *     parallel.  A call that delivers no line launches nothing new.
+ *
+ * zarc_gpu_regex_compile_ends (public and handle-less, as zarc_gpu_regex_compile) fills the same struct with the FORWARD table of R alone,
+ * without a SIGMA* loop: it reads from a match's first byte towards the line's end.
+ *   - delta[q * 256 + byte] for q < states.  DEAD = states - 1: no continuation is in L(R); every byte leads from DEAD to DEAD and a walk
+ *     stops there.  An expression that matches nothing (c^) has this one state.
+ *   - `start` = the state in front of a match's first byte when that byte is NOT its line's first.  A walk never reads a 0x0A, so that
+ *     column is free: delta[start * 256 + 0x0A] = the state in front of a match's first byte when it IS the line's first byte (where `^`
+ *     holds).  delta[q * 256 + 0x0A] == DEAD for every other q.  `start` may be DEAD itself: with ^bb a match starts at a line's first byte
+ *     or nowhere.
+ *   - accept[q] bit 0 = a match may end behind the byte just read; bit 1 = a match may end there if the line ends there (where `$` holds).
+ *     accept[start], accept[delta[start * 256 + 0x0A]] are 0 for what R's own acceptance is concerned: R consumes a byte.
+ *   - E(p): q = p == ls ? delta[start * 256 + 0x0A] : start; for j = p, p + 1, ... < le: q = delta[q * 256 + content[j]]; stop at DEAD;
+ *     accept[q] & 1, or accept[q] & 2 with j + 1 == le: E = j + 1.  The last such E is the match's end.
+ *   - Dialect, refusals and messages are zarc_gpu_regex_compile's.  More than ZARC_GPU_REGEX_MAX_STATES forward states (DEAD and the
+ *     line-start state included) is ZARC_GPU_E_UNSUPPORTED, the message giving the number needed: an expression that
+ *     zarc_gpu_regex_compile -- and so `-E` -- accepts can still be refused here ((a|b)*a(a|b){6} must know which of the last seven bytes were an a: 129 states). */
+typedef struct {
+    uint64_t frame;      /* index in the batch */
+    uint64_t start;      /* offset of the match's first byte in the frame's content */
+    uint64_t length;     /* the whole match in bytes, however long */
+    uint64_t number;     /* the 1-based number of the line that holds it */
+    uint64_t line_start; /* offset of that line's first byte in the frame's content */
+    uint64_t which;      /* SET: the pattern that matched (see E(p)); every other kind: ZARC_GPU_SEARCH_NONE */
+    uint64_t text_off;   /* where the delivered bytes lie in `text` */
+    uint64_t text_len;   /* min(length, max_line): the match's FIRST text_len bytes */
+} zarc_gpu_match;
+int zarc_gpu_regex_compile_ends(const void *regex, size_t regex_len, unsigned flags, zarc_gpu_regex_dfa *out /* may be NULL */, char *err, size_t err_cap);
+int zarc_gpu_search_matches_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                  const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const zarc_gpu_matcher *matcher,
+                                  uint64_t max_lines /* per frame; 0 = no limit */, uint64_t max_line /* 1..65536 */, size_t line_cap,
+                                  uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *which /* SET, or NULL */,
+                                  uint64_t *hits /* SET, or NULL */, uint64_t *lines /* n */, uint64_t *matches /* n */, zarc_gpu_match *rec, size_t rec_cap,
+                                  size_t *rec_used, void *text, size_t text_cap, size_t *text_used);
+int zarc_gpu_search_matches_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                         const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const zarc_gpu_matcher *matcher /* HOST */,
+                                         uint64_t max_lines, uint64_t max_line, size_t line_cap, uint8_t *digest /* n*32 */, int *status, uint64_t *count,
+                                         uint64_t *first, uint64_t *which /* SET, or NULL */, uint64_t *hits /* SET, or NULL */, uint64_t *lines,
+                                         uint64_t *matches, zarc_gpu_match *rec /* HOST array */, size_t rec_cap, size_t *rec_used,
+                                         void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
+
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN]);
@@ -540,7 +620,7 @@ enum {
     ZARC_GPU_T_DEC_LITS = 8,  /* decoder stage 2: Huffman literals (zarc_zdec_literals, side stream)      */
     ZARC_GPU_T_DEC_FRAMES = 9,/* decoder frame pass (zarc_zstd_frames + the inline decoder for the rest)  */
     ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan (a set: zarc_set_scan and zarc_set_which; a regex: zarc_regex_summary, _carry and _scan), summed over the parts of a call; < 0 or 0 after any other call */
-    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set or a regex: its twins of mark and emit; select_lines: zarc_lines_select_* in place of mark, carry and emit), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set or a regex: its twins of mark and emit; select_lines: zarc_lines_select_* in place of mark, carry and emit; search_matches: zarc_matches_* behind emit, in place of scan and gather), summed over the parts of a call; < 0 or 0 after any other call */
     ZARC_GPU_T_COUNT = 12
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);

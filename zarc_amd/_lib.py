@@ -52,6 +52,7 @@ EXPORTS = [
     "zarc_gpu_search_set_batch", "zarc_gpu_search_set_batch_device", "zarc_gpu_search_set_lines_batch", "zarc_gpu_search_set_lines_batch_device",
     "zarc_gpu_regex_compile", "zarc_gpu_search_regex_batch", "zarc_gpu_search_regex_batch_device", "zarc_gpu_search_regex_lines_batch",
     "zarc_gpu_search_regex_lines_batch_device", "zarc_gpu_select_lines_batch", "zarc_gpu_select_lines_batch_device",
+    "zarc_gpu_regex_compile_ends", "zarc_gpu_search_matches_batch", "zarc_gpu_search_matches_batch_device",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -69,6 +70,11 @@ class Params(ctypes.Structure):
 class Line(ctypes.Structure):
     """zarc_gpu_line: one matching line of a search_lines call"""
     _fields_ = [(n, ctypes.c_uint64) for n in ("frame", "start", "length", "number", "match", "text_off", "text_len")]
+
+
+class Match(ctypes.Structure):
+    """zarc_gpu_match: one match of a search_matches call"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("frame", "start", "length", "number", "line_start", "which", "text_off", "text_len")]
 
 
 class PatternSet(ctypes.Structure):
@@ -191,6 +197,12 @@ def load(path=None):
                                                 vp, sz, szp]
     lib.zarc_gpu_select_lines_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, mp, qp, c.c_uint64, c.c_uint64, vp, ip, u64p, u64p, u64p, u64p, u64p, u64p,
                                                        lp, sz, szp, vp, sz, szp]
+    lib.zarc_gpu_regex_compile_ends.argtypes = lib.zarc_gpu_regex_compile.argtypes
+    xp = c.POINTER(Match)
+    lib.zarc_gpu_search_matches_batch.argtypes = [vp, sz, vpp, szp, szp, vp, mp, c.c_uint64, c.c_uint64, sz, vp, ip, u64p, u64p, u64p, u64p, u64p, u64p, xp, sz, szp,
+                                                  vp, sz, szp]
+    lib.zarc_gpu_search_matches_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, mp, c.c_uint64, c.c_uint64, sz, vp, ip, u64p, u64p, u64p, u64p, u64p, u64p,
+                                                         xp, sz, szp, vp, sz, szp]
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

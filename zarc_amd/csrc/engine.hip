@@ -128,6 +128,10 @@ struct zarc_gpu {
     DevBuf d_ln_rec, d_ln_total, d_ln_text;     // the part's records, the sum of their text_len, and (host form) their text: sized by what the part delivers
     // the selected lines (zarc_gpu_select_lines_batch*): zarc_lines_select_* in place of zarc_lines_mark / _carry / _emit
     DevBuf d_sel_slices, d_sel_count;           // ZarcSelSlice of every slice; selected lines of every frame (decoder order; the hit lines go to d_ln_lines)
+    // every match of the delivered lines (zarc_gpu_search_matches_batch*): zarc_matches_* behind zarc_lines_emit*, over d_ln_rec where it lies
+    DevBuf d_regex_fwd;                         // the forward table (search_prepare)
+    DevBuf d_mt_bitoff, d_mt_bits;              // a regex: first word of every line record's start bits (and the sum); the bits, at most decoded bytes / 8 + 4 per record
+    DevBuf d_mt_counts, d_mt_prefix, d_mt_rec;  // matches of every line record; their exclusive sums (and the total); the part's match records
     bool vout_busy = false;     // a repack pass is between its halves: d_vout is not the check's to take
     uint64_t dec_scratch = 0;   // decoder scratch (sequences, literals, tables) of the most recent decode, as counted against the budget
     // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
@@ -640,7 +644,15 @@ struct PackPlanned {
 // ... and gathers the matching lines (zarc_gpu_search_lines_batch*).  The parts of a call -- chunks of the host form, halves of
 // unpack_device_split -- are contiguous ranges of the caller's frames processed in the caller's order, so the running remainder of rec_cap in
 // `run` gives every frame the same records however the call is cut.
-struct LinesRun { size_t rec_used = 0; uint64_t text_used = 0; float ms = 0; }; // one per call
+struct LinesRun { size_t rec_used = 0; uint64_t text_used = 0; float ms = 0; size_t match_used = 0; }; // one per call (matches: rec_used counts the lines that took part, match_used the records)
+// zarc_gpu_search_matches_batch*: the lines of `ln` stay on the device (ln.rec_cap is the call's line_cap) and their matches are delivered
+struct MatchesReq {
+    bool on;
+    uint64_t *matches;         // host, in the caller's order, this part's first frame first
+    zarc_gpu_match *rec;       // host: the call's records
+    size_t rec_cap;
+    const ZarcRegexDfa *d_fwd; // REGEX; device: the forward table
+};
 struct LinesReq {
     uint64_t max_lines;        // per frame; 0 = no limit
     uint32_t max_line;
@@ -654,6 +666,7 @@ struct LinesReq {
     bool select;               // zarc_gpu_select_lines_batch* with an ACTIVE selection: deliver the selected lines `sel` describes; lines[] counts the hit lines
     ZarcSelect sel;
     uint64_t *selected;        // zarc_gpu_select_lines_batch*; host, as lines (an inactive selection: the plain kernels run, selected == lines)
+    MatchesReq mt;
 };
 // What to search for, as search_prepare has put it on the device: one of three kinds, each with the fields its kernels take
 struct Matcher {
@@ -679,11 +692,12 @@ SearchReq part_of(SearchReq r, size_t a)
 {
     r.count += a; r.first += a;
     if (r.which) r.which += a;
-    if (r.lines) { r.ln.lines += a; r.ln.frame0 += a; if (r.ln.selected) r.ln.selected += a; }
+    if (r.lines) { r.ln.lines += a; r.ln.frame0 += a; if (r.ln.selected) r.ln.selected += a; if (r.ln.mt.on) r.ln.mt.matches += a; }
     return r;
 }
 int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
 static_assert(sizeof(ZarcLineRec) == sizeof(zarc_gpu_line), "the device's record is the caller's");
+static_assert(sizeof(ZarcMatchRec) == sizeof(zarc_gpu_match), "the device's record is the caller's");
 
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, void *d_dst_base,
                         const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk,
@@ -1313,6 +1327,127 @@ void search_scatter(const DecodedPart &p, const SearchReq &srch, const SearchPar
     for (size_t k = 0; k < sp.hits.size(); k++) srch.hits[k] += sp.hits[k]; // (32-bit per part, 64-bit over the call)
 }
 
+// matches: the lines' delivery rule with line_cap, the line records of this part (they stay on the device), the matches of every one of them,
+// the record rule over their sums, then records and text of the matches this part delivers.  Waits three times: for the sums, for the
+// records (their text is sized by them) and for the text.
+int matches_deliver(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
+{
+    zarc_gpu *const h = p.h;
+    const Matcher &mt = srch.match;
+    const size_t n = p.n;
+    const LinesReq &ln = srch.ln;
+    const MatchesReq &mq = ln.mt;
+    LinesRun &run = *ln.run;
+    int rc;
+    std::vector<uint32_t> where(n); // the decoder's index of the caller's frame
+    for (size_t i = 0; i < n; i++) where[p.order[i]] = (uint32_t)i;
+    std::vector<uint64_t> base(n);
+    std::vector<uint32_t> deliver(n);
+    uint64_t nrec = 0;
+    for (size_t c = 0; c < n; c++) {
+        const uint32_t i = where[c];
+        ln.lines[c] = sp.lines[i];
+        mq.matches[c] = 0;
+        uint64_t d = sp.lines[i];
+        if (ln.max_lines && d > ln.max_lines) d = ln.max_lines;
+        d = std::min<uint64_t>(d, ln.rec_cap - run.rec_used - nrec);
+        base[i] = nrec; deliver[i] = (uint32_t)d;
+        nrec += d;
+    }
+    if (!nrec) return ZARC_GPU_OK;
+    if ((rc = upload_u64(h, h->d_ln_base, base.data(), n))) return rc;
+    if ((rc = upload_u32(h, h->d_ln_deliver, deliver.data(), n))) return rc;
+    ZHIP(h->d_ln_rec.reserve(nrec * sizeof(ZarcLineRec)));
+    ZHIP(h->d_ln_total.reserve(8));
+    ZHIP(h->d_mt_counts.reserve(nrec * 4));
+    ZHIP(h->d_mt_prefix.reserve((nrec + 1) * 8));
+    ZHIP(hipMemsetAsync(h->d_ln_rec.p, 0, nrec * sizeof(ZarcLineRec), h->stream)); // (a record nobody wrote is an empty line of frame 0: no match)
+    ZHIP(hipMemsetAsync(h->d_mt_counts.p, 0, nrec * 4, h->stream));
+    int e8, e9;
+    ZHIP(p.t.mark(&e8));
+    const dim3 per_slice((unsigned)sp.slices), per_line((unsigned)((nrec + 255) / 256));
+    const uint64_t *const d_slices = h->d_srch_slices.as<uint64_t>(), *const d_raw = h->d_raw_len.as<uint64_t>(), *const d_rbase = h->d_ln_base.as<uint64_t>();
+    const ZarcLineSlice *const d_ln = h->d_ln_slices.as<ZarcLineSlice>();
+    const uint32_t *const d_deliver = h->d_ln_deliver.as<uint32_t>();
+    ZarcLineRec *const d_lrec = h->d_ln_rec.as<ZarcLineRec>();
+    uint32_t *const d_counts = h->d_mt_counts.as<uint32_t>();
+    uint64_t *const d_prefix = h->d_mt_prefix.as<uint64_t>();
+    switch (mt.kind) {
+    case Matcher::PATTERN:
+        hipLaunchKernelGGL(zarc_lines_emit, per_slice, dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, mt.pattern.d_bytes, mt.pattern.m, mt.icase,
+                           d_ln, d_rbase, d_deliver, ln.max_line, d_lrec);
+        hipLaunchKernelGGL(zarc_matches_count, per_line, dim3(256), 0, h->stream, nrec, d_lrec, p.d_base, p.d_off, mt.pattern.d_bytes, mt.pattern.m, mt.icase, d_counts);
+        break;
+    case Matcher::SET:
+        hipLaunchKernelGGL(zarc_lines_emit_set, per_slice, dim3(256), sp.set_lds, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, *mt.set, h->d_set.as<uint32_t>(),
+                           mt.icase, d_ln, d_rbase, d_deliver, ln.max_line, d_lrec);
+        hipLaunchKernelGGL(zarc_matches_count_set, per_line, dim3(256), sp.set_lds, h->stream, nrec, d_lrec, p.d_base, p.d_off, *mt.set, h->d_set.as<uint32_t>(), mt.icase,
+                           d_counts);
+        break;
+    case Matcher::REGEX: {
+        hipLaunchKernelGGL(zarc_lines_emit_regex, per_slice, dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, mt.d_regex, h->d_re_entry.as<uint8_t>(),
+                           d_ln, d_rbase, d_deliver, ln.max_line, d_lrec);
+        // the lines' start bits: a bit per byte of every delivered line, rounded up to words per line
+        uint64_t total_raw = 0;
+        for (size_t i = 0; i < n; i++) total_raw += p.raw_len[i];
+        ZHIP(h->d_mt_bitoff.reserve((nrec + 1) * 8));
+        ZHIP(h->d_mt_bits.reserve(total_raw / 8 + nrec * 4 + 8));
+        hipLaunchKernelGGL(zarc_matches_scan, dim3(1), dim3(256), 0, h->stream, 0u, nrec, d_lrec, (const uint32_t *)nullptr, (ZarcMatchRec *)nullptr, h->d_mt_bitoff.as<uint64_t>());
+        hipLaunchKernelGGL(zarc_matches_count_regex, per_line, dim3(256), 0, h->stream, nrec, d_lrec, p.d_base, p.d_off, mt.d_regex, mq.d_fwd, h->d_mt_bitoff.as<uint64_t>(),
+                           h->d_mt_bits.as<uint32_t>(), d_counts);
+        break; }
+    }
+    hipLaunchKernelGGL(zarc_matches_scan, dim3(1), dim3(256), 0, h->stream, 1u, nrec, d_lrec, d_counts, (ZarcMatchRec *)nullptr, d_prefix);
+    ZHIP(hipGetLastError());
+    std::vector<uint64_t> prefix(nrec + 1);
+    ZHIP(hipMemcpyAsync(prefix.data(), d_prefix, (nrec + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    ZHIP(hipStreamSynchronize(h->stream));
+    for (size_t i = 0; i < n; i++) mq.matches[p.order[i]] = prefix[base[i] + deliver[i]] - prefix[base[i]];
+    run.rec_used += nrec;
+    const uint64_t nm = std::min<uint64_t>(prefix[nrec], mq.rec_cap - run.match_used); // records are in (frame, start) order: the part's first nm matches
+    if (!nm) { ZHIP(p.t.mark(&e9)); sp.lines_ms2 = elapsed(h, e8, e9); return ZARC_GPU_OK; }
+    ZHIP(h->d_mt_rec.reserve(nm * sizeof(ZarcMatchRec)));
+    ZHIP(hipMemsetAsync(h->d_mt_rec.p, 0, nm * sizeof(ZarcMatchRec), h->stream));
+    ZarcMatchRec *const d_mrec = h->d_mt_rec.as<ZarcMatchRec>();
+    switch (mt.kind) {
+    case Matcher::PATTERN:
+        hipLaunchKernelGGL(zarc_matches_emit, per_line, dim3(256), 0, h->stream, nrec, d_lrec, p.d_base, p.d_off, mt.pattern.d_bytes, mt.pattern.m, mt.icase, d_prefix, nm,
+                           ln.max_line, d_mrec);
+        break;
+    case Matcher::SET:
+        hipLaunchKernelGGL(zarc_matches_emit_set, per_line, dim3(256), sp.set_lds, h->stream, nrec, d_lrec, p.d_base, p.d_off, *mt.set, h->d_set.as<uint32_t>(), mt.icase,
+                           d_prefix, nm, ln.max_line, d_mrec);
+        break;
+    case Matcher::REGEX:
+        hipLaunchKernelGGL(zarc_matches_emit_regex, per_line, dim3(256), 0, h->stream, nrec, d_lrec, p.d_base, p.d_off, mq.d_fwd, h->d_mt_bitoff.as<uint64_t>(),
+                           h->d_mt_bits.as<uint32_t>(), d_prefix, nm, ln.max_line, d_mrec);
+        break;
+    }
+    hipLaunchKernelGGL(zarc_matches_scan, dim3(1), dim3(256), 0, h->stream, 2u, nm, d_lrec, (const uint32_t *)nullptr, d_mrec, h->d_ln_total.as<uint64_t>());
+    ZHIP(hipGetLastError());
+    uint64_t text_bytes = 0;
+    std::vector<ZarcMatchRec> recs(nm);
+    ZHIP(hipMemcpyAsync(recs.data(), d_mrec, nm * sizeof(ZarcMatchRec), hipMemcpyDeviceToHost, h->stream));
+    ZHIP(hipMemcpyAsync(&text_bytes, h->d_ln_total.p, 8, hipMemcpyDeviceToHost, h->stream));
+    ZHIP(hipStreamSynchronize(h->stream));
+    uint8_t *d_text = ln.d_text ? ln.d_text + run.text_used : nullptr;
+    if (!d_text) { ZHIP(h->d_ln_text.reserve(text_bytes + 16)); d_text = h->d_ln_text.as<uint8_t>(); } // (host form: sized by what came of the scan)
+    hipLaunchKernelGGL(zarc_matches_gather, dim3((unsigned)((nm + 3) / 4)), dim3(256), 0, h->stream, nm, d_mrec, p.d_base, p.d_off, d_text);
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&e9));
+    if (ln.h_text && text_bytes && (rc = lines_text_out(h, ln.h_text + run.text_used, d_text, text_bytes))) return rc;
+    ZHIP(hipStreamSynchronize(h->stream));
+    for (uint64_t k = 0; k < nm; k++) {
+        zarc_gpu_match &r = mq.rec[run.match_used + k];
+        memcpy(&r, &recs[k], sizeof r);
+        r.frame = ln.frame0 + p.order[recs[k].frame];
+        r.text_off += run.text_used;
+    }
+    run.match_used += nm; run.text_used += text_bytes;
+    sp.lines_ms2 = elapsed(h, e8, e9);
+    return ZARC_GPU_OK;
+}
+
 // lines, second half: the delivery rule in the caller's order, then records and text of what this part delivers.  Waits twice: for the
 // records (their text is sized by them) and for the text.
 int lines_deliver(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
@@ -1321,6 +1456,7 @@ int lines_deliver(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
     const Matcher &mt = srch.match;
     const size_t n = p.n;
     const LinesReq &ln = srch.ln;
+    if (ln.mt.on) return matches_deliver(p, srch, sp);
     LinesRun &run = *ln.run;
     int rc;
     std::vector<uint32_t> where(n); // the decoder's index of the caller's frame
@@ -2042,6 +2178,11 @@ struct LinesArgs {
     size_t text_cap, *text_used;
     const zarc_gpu_line_select *select = nullptr; // zarc_gpu_select_lines_batch*
     uint64_t *selected = nullptr;
+    // zarc_gpu_search_matches_batch*: rec_cap, rec_used, text* above are the MATCH records' (rec itself stays null); the lines have line_cap
+    bool only_matches = false;
+    size_t line_cap = 0;
+    uint64_t *matches = nullptr;
+    zarc_gpu_match *match_rec = nullptr;
 };
 
 // Every check of a search call that does not look at the frames, in the order the callers are promised (the matcher, the flags, the result
@@ -2052,7 +2193,7 @@ int search_prepare(zarc_gpu_t *h, size_t n, const MatcherArgs &a, const SearchOu
 {
     const unsigned unknown = a.flags & ~(unsigned)ZARC_GPU_SEARCH_ICASE;
     const bool no_out = !out.digest || !out.status || !out.count || !out.first;
-    zarc_gpu_regex_dfa dfa; // REGEX: compiled by the checks, uploaded below
+    zarc_gpu_regex_dfa dfa, fwd; // REGEX: compiled by the checks, uploaded below (fwd: the matches calls' forward table)
     switch (a.kind) {
     case Matcher::PATTERN:
         if (!a.text || a.text_len == 0 || a.text_len > ZARC_GPU_SEARCH_MAX_PATTERN) { set_error(h, "search: the pattern has 1 to 256 bytes"); return ZARC_GPU_E_PARAM; }
@@ -2074,12 +2215,16 @@ int search_prepare(zarc_gpu_t *h, size_t n, const MatcherArgs &a, const SearchOu
         std::string err;
         const int rc = zre::compile(a.text, a.text_len, a.flags, &dfa, err);
         if (rc) { set_error(h, err.c_str()); return rc; }
+        if (la && la->only_matches) {
+            const int rc2 = zre::compile(a.text, a.text_len, a.flags, &fwd, err, /*ends=*/true);
+            if (rc2) { set_error(h, err.c_str()); return rc2; }
+        }
         if (no_out) return ZARC_GPU_E_PARAM;
         break; }
     }
     if (la) { // -> ZARC_GPU_E_PARAM or ZARC_GPU_E_DSTSIZE
         if (!la->lines || !la->rec_used || !la->text_used) return ZARC_GPU_E_PARAM;
-        if (la->rec_cap && (!la->rec || !la->text)) return ZARC_GPU_E_PARAM;
+        if (!la->only_matches && la->rec_cap && (!la->rec || !la->text)) return ZARC_GPU_E_PARAM;
         if (la->max_line < 1 || la->max_line > ZARC_GPU_LINES_MAX_LINE) { set_error(h, "search_lines: max_line is 1 to 65536"); return ZARC_GPU_E_PARAM; }
         if (a.kind == Matcher::PATTERN && memchr(a.text, 0x0A, a.text_len)) { set_error(h, "search_lines: the pattern must not contain a newline"); return ZARC_GPU_E_PARAM; }
         if (la->rec_cap > SIZE_MAX / (size_t)la->max_line || la->text_cap < la->rec_cap * (size_t)la->max_line) { set_error(h, "search_lines: text_cap is below rec_cap * max_line"); return ZARC_GPU_E_DSTSIZE; }
@@ -2088,12 +2233,17 @@ int search_prepare(zarc_gpu_t *h, size_t n, const MatcherArgs &a, const SearchOu
             if (la->select->reserved) { set_error(h, "select_lines: reserved must be 0"); return ZARC_GPU_E_PARAM; }
             if (!la->selected) return ZARC_GPU_E_PARAM;
         }
+        if (la->only_matches && (!la->matches || (la->line_cap && la->rec_cap && (!la->match_rec || !la->text)))) return ZARC_GPU_E_PARAM;
         *la->rec_used = 0; *la->text_used = 0;
     }
     if (a.kind == Matcher::SET && out.hits) memset(out.hits, 0, a.set->count * sizeof *out.hits); // (every part adds to them)
     *req = SearchReq{Matcher{a.kind, a.flags & ZARC_GPU_SEARCH_ICASE ? 1u : 0u, {}}, out.count, out.first, out.which, out.hits, la != nullptr, LinesReq{}};
     if (la) req->ln = LinesReq{la->max_lines, (uint32_t)la->max_line, la->lines, 0, la->rec, la->rec_cap, host_text ? nullptr : (uint8_t *)la->text,
                                host_text ? (uint8_t *)la->text : nullptr, run, false, ZarcSelect{0, 0, 0}, nullptr};
+    if (la && la->only_matches) { // the line records stay on the device: their cap is line_cap
+        req->ln.rec = nullptr; req->ln.rec_cap = la->line_cap;
+        req->ln.mt = MatchesReq{true, la->matches, la->match_rec, la->rec_cap, nullptr};
+    }
     if (la && la->select) {
         req->ln.select = la->select->flags || la->select->before || la->select->after;
         req->ln.sel = ZarcSelect{la->select->flags & ZARC_GPU_SELECT_INVERT ? 1u : 0u, la->select->before, la->select->after};
@@ -2116,12 +2266,30 @@ int search_prepare(zarc_gpu_t *h, size_t n, const MatcherArgs &a, const SearchOu
         ZHIP(h->d_regex.reserve(sizeof dfa));
         ZHIP(hipMemcpy(h->d_regex.p, &dfa, sizeof dfa, hipMemcpyHostToDevice));
         req->match.d_regex = h->d_regex.as<ZarcRegexDfa>();
+        if (la && la->only_matches) {
+            ZHIP(h->d_regex_fwd.reserve(sizeof fwd));
+            ZHIP(hipMemcpy(h->d_regex_fwd.p, &fwd, sizeof fwd, hipMemcpyHostToDevice));
+            req->ln.mt.d_fwd = h->d_regex_fwd.as<ZarcRegexDfa>();
+        }
         return 0;
     }
     return 0;
 }
 
 // zarc_gpu_select_lines_batch*: the matcher description as the arguments of that kind's own lines call
+// ... and zarc_gpu_search_matches_batch*: the matcher alone
+int matches_matcher(zarc_gpu_t *h, const zarc_gpu_matcher *m, const uint64_t *which, const uint64_t *hits, MatcherArgs *a)
+{
+    if (!m) { set_error(h, "search_matches: a matcher is needed"); return ZARC_GPU_E_PARAM; }
+    switch (m->kind) {
+    case ZARC_GPU_MATCH_FIXED: *a = MatcherArgs{Matcher::PATTERN, m->text, m->text_len, nullptr, m->flags}; break;
+    case ZARC_GPU_MATCH_SET: *a = MatcherArgs{Matcher::SET, nullptr, 0, m->set, m->flags}; break;
+    case ZARC_GPU_MATCH_REGEX: *a = MatcherArgs{Matcher::REGEX, m->text, m->text_len, nullptr, m->flags}; break;
+    default: set_error(h, "search_matches: unknown matcher kind"); return ZARC_GPU_E_PARAM;
+    }
+    if (m->kind != ZARC_GPU_MATCH_SET && (which || hits)) { set_error(h, "search_matches: which and hits belong to a set"); return ZARC_GPU_E_PARAM; }
+    return 0;
+}
 int select_matcher(zarc_gpu_t *h, const zarc_gpu_matcher *m, const zarc_gpu_line_select *select, const uint64_t *which, const uint64_t *hits, MatcherArgs *a)
 {
     if (!m || !select) { set_error(h, "select_lines: a matcher and a selection are needed"); return ZARC_GPU_E_PARAM; }
@@ -2149,7 +2317,7 @@ int search_call_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (!d_frames_base || !frame_off || !frame_len || !raw_len) return ZARC_GPU_E_PARAM;
     if ((rc = check_frame_sizes(h, n, frame_len, raw_len))) return rc;
     rc = unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, out.digest, out.status, nullptr, &req);
-    if (la) { *la->rec_used = run.rec_used; *la->text_used = (size_t)run.text_used; }
+    if (la) { *la->rec_used = la->only_matches ? run.match_used : run.rec_used; *la->text_used = (size_t)run.text_used; }
     return rc;
 }
 } // namespace
@@ -2228,6 +2396,29 @@ int zarc_gpu_regex_compile(const void *regex, size_t regex_len, unsigned flags, 
     const int rc = zre::compile(regex, regex_len, flags, out, msg);
     if (err && err_cap) { const size_t k = std::min(msg.size(), err_cap - 1); memcpy(err, msg.data(), k); err[k] = 0; }
     return rc;
+}
+int zarc_gpu_regex_compile_ends(const void *regex, size_t regex_len, unsigned flags, zarc_gpu_regex_dfa *out, char *err, size_t err_cap)
+{
+    std::string msg;
+    const int rc = zre::compile(regex, regex_len, flags, out, msg, /*ends=*/true);
+    if (err && err_cap) { const size_t k = std::min(msg.size(), err_cap - 1); memcpy(err, msg.data(), k); err[k] = 0; }
+    return rc;
+}
+
+int zarc_gpu_search_matches_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                         const uint64_t *raw_len, const uint8_t *expect, const zarc_gpu_matcher *matcher, uint64_t max_lines, uint64_t max_line,
+                                         size_t line_cap, uint8_t *digest, int *status, uint64_t *count, uint64_t *first, uint64_t *which, uint64_t *hits,
+                                         uint64_t *lines, uint64_t *matches, zarc_gpu_match *rec, size_t rec_cap, size_t *rec_used, void *d_text, size_t text_cap,
+                                         size_t *text_used)
+{
+    MatcherArgs a;
+    int rc = check_common(h, n);
+    if (rc || (rc = matches_matcher(h, matcher, which, hits, &a))) return rc;
+    LinesArgs la{max_lines, max_line, lines, nullptr, rec_cap, rec_used, d_text, text_cap, text_used};
+    la.only_matches = true; la.line_cap = line_cap; la.matches = matches; la.match_rec = rec;
+    std::vector<uint64_t> own_which; // a set without `which`: the search still computes it
+    if (a.kind == Matcher::SET && !which) { own_which.resize(n + 1); which = own_which.data(); }
+    return search_call_device(h, n, d_frames_base, frame_off, frame_len, raw_len, expect, a, &la, SearchOut{digest, status, count, first, which, hits});
 }
 
 
@@ -2834,7 +3025,7 @@ int search_call_host(zarc_gpu_t *h, size_t n, const void *const *frame, const si
     if ((rc = search_prepare(h, n, a, out, la, /*host_text=*/true, &run, &req))) return rc;
     if (n == 0) return ZARC_GPU_OK;
     rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, (uint8_t (*)[ZARC_GPU_DIGEST_LEN])out.digest, out.status, &req);
-    if (la) { *la->rec_used = run.rec_used; *la->text_used = (size_t)run.text_used; }
+    if (la) { *la->rec_used = la->only_matches ? run.match_used : run.rec_used; *la->text_used = (size_t)run.text_used; }
     return rc;
 }
 } // namespace
@@ -2909,6 +3100,22 @@ int zarc_gpu_select_lines_batch(zarc_gpu_t *h, size_t n, const void *const *fram
     if (rc || (rc = select_matcher(h, matcher, select, which, hits, &a))) return rc;
     LinesArgs la{max_lines, max_line, lines, rec, rec_cap, rec_used, text, text_cap, text_used};
     la.select = select; la.selected = selected;
+    std::vector<uint64_t> own_which; // a set without `which`: the search still computes it
+    if (a.kind == Matcher::SET && !which) { own_which.resize(n + 1); which = own_which.data(); }
+    return search_call_host(h, n, frame, frame_len, raw_len, expect, a, &la, SearchOut{(uint8_t *)digest, status, count, first, which, hits});
+}
+
+int zarc_gpu_search_matches_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                                  const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const zarc_gpu_matcher *matcher, uint64_t max_lines, uint64_t max_line, size_t line_cap,
+                                  uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, uint64_t *count, uint64_t *first, uint64_t *which, uint64_t *hits,
+                                  uint64_t *lines, uint64_t *matches, zarc_gpu_match *rec, size_t rec_cap, size_t *rec_used, void *text, size_t text_cap,
+                                  size_t *text_used)
+{
+    MatcherArgs a;
+    int rc = check_common(h, n);
+    if (rc || (rc = matches_matcher(h, matcher, which, hits, &a))) return rc;
+    LinesArgs la{max_lines, max_line, lines, nullptr, rec_cap, rec_used, text, text_cap, text_used};
+    la.only_matches = true; la.line_cap = line_cap; la.matches = matches; la.match_rec = rec;
     std::vector<uint64_t> own_which; // a set without `which`: the search still computes it
     if (a.kind == Matcher::SET && !which) { own_which.resize(n + 1); which = own_which.data(); }
     return search_call_host(h, n, frame, frame_len, raw_len, expect, a, &la, SearchOut{(uint8_t *)digest, status, count, first, which, hits});

@@ -300,6 +300,25 @@ __global__ void zarc_lines_select_emit_set(uint32_t n, const uint64_t *slice_pre
 __global__ void zarc_lines_select_emit_regex(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
                                              const ZarcRegexDfa *dfa, const uint8_t *entry, ZarcSelect q, const ZarcSelSlice *slices, const uint64_t *rec_base,
                                              const uint32_t *deliver, uint32_t max_line, ZarcLineRec *rec);
+// every match of the delivered matching lines (zdec_matches.hip): a lane per line record of the part (lrec, as zarc_lines_emit* left them).
+// ZarcMatchRec is zarc_gpu_match; frame: the decoder's index.  fdfa: the forward table of zarc_gpu_regex_compile_ends.  bits: the lines'
+// start bits, record k's from word bit_off[k] on.  prefix[k]: the part's matches in front of line k; matches below `limit` get a record.
+struct ZarcMatchRec { uint64_t frame, start, length, number, line_start, which, text_off, text_len; };
+__global__ void zarc_matches_count(uint64_t nrec, const ZarcLineRec *lrec, const uint8_t *dec_base, const uint64_t *dec_off, const uint8_t *pattern, uint32_t m,
+                                   uint32_t icase, uint32_t *counts);
+__global__ void zarc_matches_count_set(uint64_t nrec, const ZarcLineRec *lrec, const uint8_t *dec_base, const uint64_t *dec_off, ZarcSetDesc sd, const uint32_t *set,
+                                       uint32_t icase, uint32_t *counts);
+__global__ void zarc_matches_count_regex(uint64_t nrec, const ZarcLineRec *lrec, const uint8_t *dec_base, const uint64_t *dec_off, const ZarcRegexDfa *dfa,
+                                         const ZarcRegexDfa *fdfa, const uint64_t *bit_off, uint32_t *bits, uint32_t *counts);
+__global__ void zarc_matches_emit(uint64_t nrec, const ZarcLineRec *lrec, const uint8_t *dec_base, const uint64_t *dec_off, const uint8_t *pattern, uint32_t m,
+                                  uint32_t icase, const uint64_t *prefix, uint64_t limit, uint32_t max_line, ZarcMatchRec *mrec);
+__global__ void zarc_matches_emit_set(uint64_t nrec, const ZarcLineRec *lrec, const uint8_t *dec_base, const uint64_t *dec_off, ZarcSetDesc sd, const uint32_t *set,
+                                      uint32_t icase, const uint64_t *prefix, uint64_t limit, uint32_t max_line, ZarcMatchRec *mrec);
+__global__ void zarc_matches_emit_regex(uint64_t nrec, const ZarcLineRec *lrec, const uint8_t *dec_base, const uint64_t *dec_off, const ZarcRegexDfa *fdfa,
+                                        const uint64_t *bit_off, const uint32_t *bits, const uint64_t *prefix, uint64_t limit, uint32_t max_line, ZarcMatchRec *mrec);
+// what 0 / 1: out[0 .. nrec] = exclusive sums (and the total) of the lines' bit words / of counts[]; 2: mrec[k].text_off, out[0] = the sum of text_len
+__global__ void zarc_matches_scan(uint32_t what, uint64_t nrec, const ZarcLineRec *lrec, const uint32_t *counts, ZarcMatchRec *mrec, uint64_t *out);
+__global__ void zarc_matches_gather(uint64_t nrec, const ZarcMatchRec *rec, const uint8_t *dec_base, const uint64_t *dec_off, uint8_t *text);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

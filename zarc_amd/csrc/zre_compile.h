@@ -17,6 +17,10 @@
 //   consumes at least one byte, so `start` has no accept bit and a 0x0A position is never marked.
 // ZARC_GPU_SEARCH_ICASE is folded into the classes here (ASCII letters only); the content is never touched.
 //
+// compile(..., ends = true) makes the second table of the matches calls (zarc_gpu_regex_compile_ends) from the same position automaton: R
+// alone, read FORWARDS from a match's first byte, stepped along the successors (pred transposed) from R's first positions, with one dead
+// state.  It answers where the match that starts here ENDS; its layout is in include/zarc_gpu.h.
+//
 // Dialect, refusals and the offsets in the messages: include/zarc_gpu.h, the section of zarc_gpu_regex_compile.
 #ifndef ZRE_COMPILE_H
 #define ZRE_COMPILE_H
@@ -410,8 +414,9 @@ inline int refuse(int code, size_t at, const std::string &why, std::string &err)
     return code;
 }
 
-// -> 0, ZARC_GPU_E_PARAM or ZARC_GPU_E_UNSUPPORTED; out may be null
-inline int compile(const void *regex, size_t len, unsigned flags, zarc_gpu_regex_dfa *out, std::string &err)
+// -> 0, ZARC_GPU_E_PARAM or ZARC_GPU_E_UNSUPPORTED; out may be null.  ends: the FORWARD table of R alone (zarc_gpu_regex_compile_ends, see
+// compile_ends below) in place of the backward table of SIGMA* . reverse(R); parsing, refusals and byte classes are the same.
+inline int compile(const void *regex, size_t len, unsigned flags, zarc_gpu_regex_dfa *out, std::string &err, bool ends = false)
 {
     err.clear();
     if (!regex || len == 0) return refuse(ZARC_GPU_E_PARAM, 0, "an empty expression", err);
@@ -503,6 +508,49 @@ inline int compile(const void *regex, size_t len, unsigned flags, zarc_gpu_regex
         return a;
     };
 
+    // The forward automaton of R alone: position 0 stands for "nothing read yet", a step goes along the successors (pred transposed) and
+    // there is no loop, so the empty set is the dead state.  The boundary symbols are read where a line allows them: BEGIN, once or more,
+    // in front of the line's first byte only (start_ls); END, once or more, behind its last only (accept bit 1).
+    std::vector<uint64_t> succ;
+    if (ends) {
+        succ.assign((size_t)(P + 1) * W, 0);
+        for (uint32_t q = 1; q <= P; q++)
+            for (uint32_t p = 1; p <= P; p++)
+                if (g.pred[(size_t)q * W + p / 64] >> (p & 63) & 1) succ[(size_t)p * W + q / 64] |= 1ull << (q & 63);
+    }
+    auto fstep = [&](const Bits &from, const Bits &sym) {
+        Bits u(W, 0);
+        for (uint32_t k = 0; k < W; k++) {
+            uint64_t bits = from[k];
+            while (bits) {
+                const uint32_t p = k * 64 + (uint32_t)__builtin_ctzll(bits);
+                bits &= bits - 1;
+                const uint64_t *row = p ? &succ[(size_t)p * W] : first_r.data();
+                for (uint32_t j = 0; j < W; j++) u[j] |= row[j];
+            }
+        }
+        for (uint32_t j = 0; j < W; j++) u[j] &= sym[j];
+        return u;
+    };
+    auto faccept_of = [&](const Bits &q) {
+        uint8_t a = meets(q, last_r) ? 1 : 0;
+        Bits b = fstep(q, reads[END]);
+        for (uint32_t k = 0; k <= P; k++) { // (no loop: the sets need not grow, but a chain of anchors is at most P long)
+            if (meets(b, last_r)) { a |= 2; break; }
+            b = fstep(b, reads[END]);
+        }
+        return a;
+    };
+    Bits start_ls = init; // ends: the state in front of a line's first byte
+    if (ends) {
+        start = init;
+        Bits b = init;
+        for (uint32_t k = 0; k <= P; k++) {
+            b = fstep(b, reads[BEGIN]);
+            for (uint32_t j = 0; j < W; j++) start_ls[j] |= b[j];
+        }
+    }
+
     // subset construction from `start` over the byte classes
     std::map<Bits, uint32_t> ids;
     std::vector<Bits> states;
@@ -510,10 +558,19 @@ inline int compile(const void *regex, size_t len, unsigned flags, zarc_gpu_regex
     std::vector<uint8_t> acc;
     ids.emplace(start, 0);
     states.push_back(start);
+    uint32_t ls_id = 0, dead_id = 0;
+    if (ends) { // the line-start state and the dead state are states whether or not a byte leads to them
+        for (const Bits *b : {(const Bits *)&start_ls, (const Bits *)nullptr}) {
+            const Bits s = b ? *b : Bits(W, 0);
+            auto it = ids.find(s);
+            if (it == ids.end()) { it = ids.emplace(s, (uint32_t)states.size()).first; states.push_back(s); }
+            (b ? ls_id : dead_id) = it->second;
+        }
+    }
     for (uint32_t q = 0; q < states.size(); q++) {
-        acc.push_back(accept_of(states[q]));
+        acc.push_back(ends ? faccept_of(states[q]) : accept_of(states[q]));
         for (uint32_t c = 0; c < ncls; c++) {
-            Bits to = step(states[q], reads[c]);
+            Bits to = ends ? fstep(states[q], reads[c]) : step(states[q], reads[c]);
             auto it = ids.find(to);
             if (it == ids.end()) {
                 if (states.size() >= MAX_SUBSET) {
@@ -551,6 +608,21 @@ inline int compile(const void *regex, size_t len, unsigned flags, zarc_gpu_regex
         char msg[128];
         snprintf(msg, sizeof msg, "needs %u states; the limit is %d", nblocks, ZARC_GPU_REGEX_MAX_STATES);
         return refuse(ZARC_GPU_E_UNSUPPORTED, 0, msg, err);
+    }
+    if (ends && out) { // the dead state is the last one; the 0x0A column, which no walk reads, holds the line-start state at `start`
+        const uint32_t dead = block[dead_id], last = nblocks - 1;
+        auto name = [&](uint32_t b) { return b == dead ? last : b == last ? dead : b; };
+        memset(out, 0, sizeof *out);
+        out->states = nblocks;
+        out->start = name(block[0]);
+        for (uint32_t q = 0; q < N; q++) {
+            const uint32_t b = name(block[q]);
+            out->accept[b] = acc[q];
+            for (unsigned c = 0; c < 256; c++) out->delta[b * 256 + c] = (uint8_t)name(block[trans[(size_t)q * ncls + cls[c]]]);
+        }
+        for (uint32_t b = 0; b < nblocks; b++) out->delta[b * 256 + 0x0A] = (uint8_t)last;
+        out->delta[out->start * 256 + 0x0A] = (uint8_t)name(block[ls_id]);
+        return 0;
     }
     if (out) {
         memset(out, 0, sizeof *out);

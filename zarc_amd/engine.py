@@ -625,6 +625,81 @@ class Engine:
             self.free(d_text)
         return self._select_result(kind, n, status, dig, count, first, which, hits[:len(what)] if is_set else None, lines, selected, rec, rec_used.value, text)
 
+    # ---- only the matches (zarc_gpu_search_matches_batch*): grep -o ----
+    @staticmethod
+    def _matches_result(kind, n, status, dig, count, first, which, hits, lines, matches, rec, rec_used, text):
+        none = lambda v: None if int(v) == _lib.SEARCH_NONE else int(v)
+        mid = (lambda i: (none(which[i]),)) if kind == _lib.MATCH_SET else (lambda i: ())
+        results = [(int(status[i]), bytes(dig[i]), int(count[i]), none(first[i])) + mid(i) + (int(lines[i]), int(matches[i])) for i in range(n)]
+        records = [(r.frame, r.start, r.length, r.number, r.line_start, none(r.which), text[r.text_off:r.text_off + r.text_len]) for r in rec[:rec_used]]
+        return results, records, ([int(v) for v in hits] if kind == _lib.MATCH_SET else None)
+
+    def search_matches(self, frames, raw_lens, kind, what, icase=False, expect=None, max_lines=0, max_line=4096, line_cap=4096, rec_cap=4096):
+        """Every match of the matching lines, as grep -o cuts them out -> (results, records, hits).  kind / what as select_lines().
+        results[i] = (status, digest, count, first[, which], lines, matches): the matcher's plain lines answer and the matches in the
+        frame's first min(lines, max_lines, what line_cap leaves) matching lines.  records = (frame, start, length, number, line_start,
+        which, text) per match in (frame, start) order, at most rec_cap of them; text: the match's first min(length, max_line) bytes;
+        which: a set's pattern, else None.  hits: a set's per-pattern counts, else None."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        count, first, which, lines, matches = ((ctypes.c_uint64 * n)() for _ in range(5))
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        m = _lib.MatcherDesc.of(kind, what, _lib.SEARCH_ICASE if icase else 0)
+        is_set = kind == _lib.MATCH_SET
+        hits = (ctypes.c_uint64 * max(len(what), 1))() if is_set else None
+        rec = (_lib.Match * max(rec_cap, 1))()
+        rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
+        text_cap = rec_cap * max_line
+        text = np.empty(max(text_cap, 1), dtype=np.uint8)
+        self._check(self.lib.zarc_gpu_search_matches_batch(
+            self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None, ctypes.byref(m), max_lines, max_line, line_cap,
+            dig.ctypes.data_as(ctypes.c_void_p), status, count, first, which if is_set else None, hits, lines, matches, rec, rec_cap, ctypes.byref(rec_used),
+            text.ctypes.data_as(ctypes.c_void_p), text_cap, ctypes.byref(text_used)))
+        return self._matches_result(kind, n, status, dig, count, first, which, hits[:len(what)] if is_set else None, lines, matches, rec, rec_used.value,
+                                    bytes(text[:text_used.value]))
+
+    def search_matches_device(self, d_frames, frame_off, frame_len, raw_len, kind, what, icase=False, expect=None, max_lines=0, max_line=4096, line_cap=4096,
+                              rec_cap=4096):
+        """search_matches() over frames on the device; the text is gathered into a device buffer of rec_cap * max_line bytes and copied back"""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        count, first, which, lines, matches = ((ctypes.c_uint64 * max(n, 1))() for _ in range(5))
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        m = _lib.MatcherDesc.of(kind, what, _lib.SEARCH_ICASE if icase else 0)
+        is_set = kind == _lib.MATCH_SET
+        hits = (ctypes.c_uint64 * max(len(what), 1))() if is_set else None
+        rec = (_lib.Match * max(rec_cap, 1))()
+        rec_used, text_used = ctypes.c_size_t(), ctypes.c_size_t()
+        text_cap = rec_cap * max_line
+        d_text = self.malloc(max(text_cap, 1))
+        try:
+            self._check(self.lib.zarc_gpu_search_matches_batch_device(
+                self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None, ctypes.byref(m),
+                max_lines, max_line, line_cap, dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), count, first,
+                which if is_set else None, hits, lines, matches, rec, rec_cap, ctypes.byref(rec_used), ctypes.c_void_p(d_text), text_cap, ctypes.byref(text_used)))
+            text = bytes(self.d2h(d_text, text_used.value)) if text_used.value else b""
+        finally:
+            self.free(d_text)
+        return self._matches_result(kind, n, status, dig, count, first, which, hits[:len(what)] if is_set else None, lines, matches, rec, rec_used.value, text)
+
+    def regex_compile_ends(self, regex, icase=False):
+        """-> (states, start, accept, delta): the FORWARD table a matches call walks from a match's first byte to find its end (layout:
+        include/zarc_gpu.h, zarc_gpu_regex_compile_ends).  Raises as search_matches() does.  Needs no device."""
+        return regex_compile(self.lib, regex, icase, ends=True)
+
     def repack(self, frames, raw_lens, expect=None):
         """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with
         the handle's current parameters -- the bytes pack() makes of what unpack() delivers -- and every other one gives None.  Only the
@@ -648,12 +723,12 @@ class Engine:
         return new, [bytes(d) for d in dig], [int(x) for x in status]
 
 
-def regex_compile(lib, regex, icase=False):
-    """Engine.regex_compile without a handle: `lib` is what _lib.load() returns"""
+def regex_compile(lib, regex, icase=False, ends=False):
+    """Engine.regex_compile (ends: regex_compile_ends) without a handle: `lib` is what _lib.load() returns"""
     pat = bytes(regex)
     dfa = _lib.RegexDfa()
     err = ctypes.create_string_buffer(512)
-    rc = lib.zarc_gpu_regex_compile(ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0, ctypes.byref(dfa), err, len(err))
+    rc = (lib.zarc_gpu_regex_compile_ends if ends else lib.zarc_gpu_regex_compile)(ctypes.cast(ctypes.c_char_p(pat), ctypes.c_void_p), len(pat), _lib.SEARCH_ICASE if icase else 0, ctypes.byref(dfa), err, len(err))
     if rc != _lib.OK:
         raise _lib.ZarcGpuError(rc, lib.zarc_gpu_error_name(rc).decode(), err.value.decode("latin-1"))
     return dfa.states, dfa.start, bytes(dfa.accept[:dfa.states]), bytes(dfa.delta[:dfa.states * 256])

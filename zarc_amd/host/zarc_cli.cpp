@@ -196,7 +196,7 @@ int usage()
                          "         --keep-smaller copies a frame unchanged when its new form is not smaller.  A frame that is not good ends the run with\n"
                          "         exit status 1 and nothing is left at PATH\n"
                          "       zarc grep [-i] [-l] [-b] [--hex] [--filter REGEX]... [--verify DIGEST] [--gpus N]\n"
-                         "                 [--lines] [-n] [-c] [-a] [-m NUM] [--max-line BYTES] [--batch-lines N] [-v] [-A NUM] [-B NUM] [-C NUM] PATTERN ARCHIVE\n"
+                         "                 [--lines] [-n] [-c] [-a] [-m NUM] [--max-line BYTES] [--batch-lines N] [-v] [-A NUM] [-B NUM] [-C NUM] [--only-matching] PATTERN ARCHIVE\n"
                          "       zarc grep ... (-e PATTERN | -f FILE)... [--tally] ARCHIVE\n"
                          "       zarc grep -E ... (PATTERN | (-e PATTERN | -f FILE)...) ARCHIVE\n"
                          "         searches the content of the files for PATTERN on the device, each distinct frame once, and writes nothing.  PATTERN is a\n"
@@ -225,6 +225,12 @@ int usage()
                          "         boundaries.  COUNT is the number of positions at which a match starts; several -e and the lines of -f FILE are joined as\n"
                          "         (A)|(B)|...  An expression that is refused, or whose automaton needs more than 64 states, ends the run with exit status 2\n"
                          "         before ARCHIVE is opened.  --hex and --tally do not go with -E\n"
+                         "         --only-matching (grep's -o; spelled out only) prints every match of a matching line instead of the line, cut out on the device, one per output line:\n"
+                         "         PATH:[NUMBER:][OFFSET:]MATCH, the longest match at the leftmost position and on from its end, as grep -o.  -b gives the offset\n"
+                         "         of the match itself, -m NUM counts lines, -c and -l ignore it, --max-line cuts a match and the binary-file rule looks at the\n"
+                         "         matches.  --batch-lines N bounds the lines that take part in one device call and the matches it brings back.  With -E the\n"
+                         "         expression needs a second table of at most 64 states: one that -E accepts can be refused with it, before ARCHIVE is opened.\n"
+                         "         It does not go with -v, -A, -B, -C or --tally\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -767,6 +773,7 @@ int cmd_grep(const std::vector<std::string> &a)
     std::vector<std::string> typed; // -e / -f: the patterns of a set, as given
     bool use_set = false, tally = false;
     bool ere = false; // -E: PATTERN is a regular expression (zarc_gpu_search_regex_batch*)
+    bool only = false; // --only-matching (grep's -o; the short form stays the usage error it was): every match of the matching lines in place of the lines (zarc_gpu_search_matches_batch); selects lines mode
     zarc::LineSelect sel; // -v, -A, -B, -C: the selected lines (zarc_gpu_select_lines_batch); any of them selects lines mode
     auto context = [&](char which, const std::string &num) { // -A NUM, -B NUM, -C NUM; false: not a number
         if (num.empty() || num.find_first_not_of("0123456789") != std::string::npos) return false;
@@ -802,6 +809,7 @@ int cmd_grep(const std::vector<std::string> &a)
         else if (options && a[i] == "--gpus" && i + 1 < a.size()) gpus = std::atoi(a[++i].c_str());
         else if (options && a[i] == "--hex") hex = true;
         else if (options && a[i] == "--extended-regexp") ere = true;
+        else if (options && a[i] == "--only-matching") only = lines_mode = true;
         else if (options && a[i] == "--") options = false;
         else if (options && a[i].size() >= 2 && a[i][0] == '-' && a[i][1] != '-') { // -i -l -b -F, alone or bundled
             for (size_t k = 1; k < a[i].size(); k++) {
@@ -835,6 +843,8 @@ int cmd_grep(const std::vector<std::string> &a)
     } else typed.push_back(pattern);
     if (!have_pattern || input.empty() || gpus < 1 || gpus > 64) return usage();
     if (sel.active() && tally) return usage(); // the tally counts positions: there is no line to select
+    if (only && (sel.active() || tally)) return usage(); // a line without a match, a context line and the tally have no match to print
+    if (count_lines || names_only) only = false; // as in GNU grep with -o: -c and -l count and name what they would without it
     if (ere) { // several expressions are one alternation, as in grep; a bad one is refused here, before the archive is opened
         if (hex || tally) return usage();
         std::string joined;
@@ -842,6 +852,10 @@ int cmd_grep(const std::vector<std::string> &a)
         char why[256];
         if (zarc_gpu_regex_compile(joined.data(), joined.size(), icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, nullptr, why, sizeof why) != ZARC_GPU_OK) {
             std::fprintf(stderr, "Error: %s\n", why);
+            return 2;
+        }
+        if (only && zarc_gpu_regex_compile_ends(joined.data(), joined.size(), icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, nullptr, why, sizeof why) != ZARC_GPU_OK) {
+            std::fprintf(stderr, "Error: --only-matching: %s\n", why); // (the table that finds a match's end is a second one: it can be too large where the first is not)
             return 2;
         }
         typed.assign(1, joined);
@@ -905,6 +919,74 @@ int cmd_grep(const std::vector<std::string> &a)
             auto &v = files_of[*f.digest];
             if (v.empty()) order.push_back(*f.digest);
             v.push_back(i);
+        }
+        if (lines_mode && only) {
+            // ---- --only-matching: every match of the matching lines (zarc_gpu_search_matches_batch), printed per file in directory order as
+            // PATH:[NUMBER:][OFFSET:]MATCH.  -m NUM counts lines, as in GNU grep.  One call lets at most --batch-lines lines take part and
+            // brings back at most --batch-lines matches; frames behind the one at which either ran out are searched again in a following
+            // call, and a frame that is first in its call and still has more than fit prints what it got and says so.
+            zarc::MatchWhat what;
+            what.kind = use_set ? ZARC_GPU_MATCH_SET : ere ? ZARC_GPU_MATCH_REGEX : ZARC_GPU_MATCH_FIXED;
+            what.text = pattern; what.set = set;
+            const uint64_t per_frame = (uint64_t)max_per_file;
+            std::map<zarc::Digest, zarc::FrameReader::Result> done;
+            std::map<zarc::Digest, uint64_t> lines_in; // the lines of the frame that took part
+            const size_t BATCH = (size_t)1 << 30;
+            size_t at = 0;
+            for (const zarc::Digest &d : order) bytes += rd.frames().at(d).uncompressed;
+            while (at < order.size()) {
+                std::vector<zarc::Digest> batch;
+                for (size_t batch_bytes = 0; at + batch.size() < order.size() && batch_bytes < BATCH; batch_bytes += (size_t)rd.frames().at(batch.back()).uncompressed)
+                    batch.push_back(order[at + batch.size()]);
+                std::vector<zarc::FrameReader::Result> res = rd.search_matches(batch, what, icase, per_frame, (uint64_t)max_line, (size_t)batch_lines, (size_t)batch_lines);
+                LOGF(3, "search_matches", "frames=%zu", batch.size());
+                size_t taken = batch.size();
+                uint64_t lines_left = (uint64_t)batch_lines;
+                for (size_t k = 0; k < batch.size(); k++) {
+                    const uint64_t want = per_frame ? std::min<uint64_t>(res[k].lines, per_frame) : res[k].lines;
+                    const uint64_t got = std::min<uint64_t>(want, lines_left);
+                    if (k > 0 && (got < want || res[k].match_records.size() < res[k].matches)) { taken = k; break; } // a cap ran out here: this frame and the rest again
+                    lines_left -= got;
+                    lines_in[batch[k]] = got;
+                    done[batch[k]] = std::move(res[k]);
+                }
+                at += taken;
+            }
+            for (size_t i = 0; i < rd.files().size(); i++) {
+                const zarc::File &f = rd.files()[i];
+                if (!f.is_normal() || !passes(filters, to_path(f.name)) || !done.count(*f.digest)) continue;
+                const zarc::FrameReader::Result &r = done.at(*f.digest);
+                const std::string path = to_path(f.name);
+                const bool decoded = r.status == ZARC_GPU_FRAME_OK || r.status == ZARC_GPU_FRAME_DIGEST;
+                if (!(decoded && r.verify.value_or(false))) {
+                    if (decoded) std::fprintf(stderr, "ERROR frame verification failed! path=%s\n", path.c_str());
+                    else std::fprintf(stderr, "ERROR %s path=%s\n", zarc_gpu_frame_status_name(r.status), path.c_str());
+                    failed++;
+                    continue;
+                }
+                if (!r.lines) continue;
+                matched++;
+                bool binary = false;
+                if (!as_text) for (const auto &x : r.match_records) binary = binary || std::memchr(x.text.data(), 0, x.text.size()) != nullptr;
+                if (binary) { std::printf("Binary file %s matches\n", path.c_str()); continue; }
+                for (const auto &x : r.match_records) {
+                    std::printf("%s:", path.c_str());
+                    if (numbers) std::printf("%llu:", (unsigned long long)x.number);
+                    if (with_offset) std::printf("%llu:", (unsigned long long)x.start);
+                    std::fwrite(x.text.data(), 1, x.text.size(), stdout);
+                    std::fputc('\n', stdout);
+                    if (x.length > x.text.size())
+                        std::fprintf(stderr, "WARN match cut path=%s line=%llu offset=%llu length=%llu\n", path.c_str(), (unsigned long long)x.number,
+                                     (unsigned long long)x.start, (unsigned long long)x.length);
+                }
+                const uint64_t shown = per_frame ? std::min<uint64_t>(r.lines, per_frame) : r.lines;
+                if (lines_in[*f.digest] < shown)
+                    std::fprintf(stderr, "WARN path=%s: the matches of %llu more matching lines not shown\n", path.c_str(), (unsigned long long)(shown - lines_in[*f.digest]));
+                if (r.match_records.size() < r.matches)
+                    std::fprintf(stderr, "WARN path=%s: %llu more matches not shown\n", path.c_str(), (unsigned long long)(r.matches - r.match_records.size()));
+            }
+            std::fprintf(stderr, "searched %llu files (%zu frames, %llu bytes), %llu match, %llu failed\n", n_files, order.size(), bytes, matched, failed);
+            return failed ? 2 : (matched ? 0 : 1);
         }
         if (lines_mode) {
             // ---- lines mode: the matching lines of every distinct frame (zarc_gpu_search_lines_batch), printed per file in directory order.

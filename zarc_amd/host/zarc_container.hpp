@@ -509,6 +509,20 @@ class ArchiveReader {
         }
         return reader_.lines_regex_content_frames(data_, len_, wanted, regex, icase, max_lines, max_line, rec_cap, sel);
     }
+    // Every match of the matching lines of every frame (FrameReader::matches_content_frames; grep -o): per digest, in order, `lines`,
+    // `matches` and the match records the two delivery rules give it; only the delivered matches' bytes come back
+    std::vector<FrameReader::Result> search_matches(const std::vector<Digest> &digests, const MatchWhat &what, bool icase = false, uint64_t max_lines = 0,
+                                                    uint64_t max_line = 4096, size_t line_cap = (size_t)1 << 20, size_t rec_cap = (size_t)1 << 20,
+                                                    std::vector<uint64_t> *hits = nullptr)
+    {
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.matches_content_frames(data_, len_, wanted, what, icase, max_lines, max_line, line_cap, rec_cap, hits);
+    }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()
     {

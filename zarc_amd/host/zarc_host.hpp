@@ -366,6 +366,13 @@ struct LineSelect {
     bool active() const { return invert || before || after; }
 };
 
+// What a matches call searches for (zarc_gpu_matcher): one fixed string or one regular expression (text), or a set of fixed strings
+struct MatchWhat {
+    int kind = ZARC_GPU_MATCH_FIXED; // ZARC_GPU_MATCH_*
+    std::string text;
+    std::vector<std::string> set;
+};
+
 // Decoder::read_content_frame + FrameIterator for a batch of frames of one archive image held in memory.
 // The reference's read side is a serial loop over frames that each get a fresh reader and DCtx (zarc-cli/src/unpack.rs:62-88,
 // decode/zstd_iterator.rs:28-29): frames are as independent on the way out as on the way in.  A FrameReader constructed with G
@@ -387,6 +394,11 @@ class FrameReader {
         uint64_t lines = 0;
         uint64_t selected = 0;           // with a LineSelect: the lines it selects (lines: the hit lines); without one: lines
         std::vector<Line> line_records;  // a selected line without a match: match == ZARC_GPU_SEARCH_NONE
+        // matches_content_frames: the matches in those of the frame's matching lines that took part, all of them counted, and the records of
+        // those that were delivered (zarc_gpu_match; text: the match's first min(length, max_line) bytes; which: a set's pattern)
+        struct Match { uint64_t start, length, number, line_start, which; std::vector<uint8_t> text; };
+        uint64_t matches = 0;
+        std::vector<Match> match_records;
     };
     explicit FrameReader(int device = 0) : FrameReader(std::vector<int>{device}) {}
     explicit FrameReader(const std::vector<int> &devices)
@@ -508,6 +520,53 @@ class FrameReader {
         return out;
     }
 
+    // Every match of the matching lines, cut out on the device (zarc_gpu_search_matches_batch; grep -o): per frame `lines`, `matches` and
+    // the records the two delivery rules give it -- the frame's first min(lines, max_lines or all, what line_cap leaves) matching lines take
+    // part, and of their matches the first that rec_cap leaves room for are delivered.  Every handle runs its share with the caller's caps.
+    // Should line_cap run out over the merged list, the shares run once more, each with the lines the rule leaves its frames (they are the
+    // caller's frames in the caller's order, so the sum of their allotments as a handle's line_cap gives every one of them exactly its
+    // own); rec_cap is then applied on the merged list.  The results are identical for every number of handles.
+    std::vector<Result> matches_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const MatchWhat &what,
+                                               bool icase = false, uint64_t max_lines = 0, uint64_t max_line = 4096, size_t line_cap = (size_t)1 << 20,
+                                               size_t rec_cap = (size_t)1 << 20, std::vector<uint64_t> *hits = nullptr)
+    {
+        if (what.kind == ZARC_GPU_MATCH_SET) check_set(what.set, true);
+        else if (what.kind == ZARC_GPU_MATCH_REGEX) { check_regex(what.text, icase); check_regex_ends(what.text, icase); }
+        else if (what.kind == ZARC_GPU_MATCH_FIXED) {
+            if (what.text.empty() || what.text.size() > ZARC_GPU_SEARCH_MAX_PATTERN) throw Error(ZARC_GPU_E_PARAM, "the pattern has 1 to 256 bytes");
+            if (what.text.find('\n') != std::string::npos) throw Error(ZARC_GPU_E_PARAM, "the pattern must not contain a newline");
+        } else throw Error(ZARC_GPU_E_PARAM, "unknown matcher kind");
+        if (max_line < 1 || max_line > ZARC_GPU_LINES_MAX_LINE) throw Error(ZARC_GPU_E_PARAM, "max_line is 1 to 65536");
+        Search s{&what.text, icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, true, max_lines, max_line, rec_cap};
+        s.regex = what.kind == ZARC_GPU_MATCH_REGEX;
+        if (what.kind == ZARC_GPU_MATCH_SET) { s.set = &what.set; s.hits = hits; }
+        s.matches = true; s.line_cap = line_cap;
+        if (s.hits) s.hits->assign(what.set.size(), 0);
+        std::vector<Result> out = run_frames(archive, archive_len, wanted, false, &s);
+        auto allot = [&](const Result &r) { return max_lines ? std::min<uint64_t>(r.lines, max_lines) : r.lines; };
+        uint64_t asked = 0;
+        for (const Result &r : out) asked += allot(r);
+        if (engines_.size() > 1 && asked > line_cap) { // a handle saw fewer lines in front of a frame than the call has: once more, with every frame's own allotment
+            std::vector<size_t> rl(wanted.size());
+            for (size_t i = 0; i < wanted.size(); i++) rl[i] = wanted[i].uncompressed;
+            const auto share = shard_assign(rl.data(), rl.size(), engines_.size());
+            std::vector<uint64_t> mine(out.size());
+            uint64_t left = line_cap;
+            for (size_t i = 0; i < out.size(); i++) { mine[i] = std::min<uint64_t>(allot(out[i]), left); left -= mine[i]; }
+            std::vector<size_t> caps(engines_.size(), 0);
+            for (size_t d = 0; d < share.size(); d++) for (size_t i : share[d]) caps[d] += (size_t)mine[i];
+            s.share_line_cap = &caps;
+            if (s.hits) s.hits->assign(what.set.size(), 0);
+            out = run_frames(archive, archive_len, wanted, false, &s);
+        }
+        size_t left = rec_cap;
+        for (Result &r : out) { // the record rule over the merged list (a handle saw fewer frames in front of this one: it delivered no less)
+            if (r.match_records.size() > left) r.match_records.resize(left);
+            left -= r.match_records.size();
+        }
+        return out;
+    }
+
   private:
     struct Search {
         const std::string *pattern; unsigned flags; bool lines = false; uint64_t max_lines = 0, max_line = 0; size_t rec_cap = 0;
@@ -515,7 +574,16 @@ class FrameReader {
         const std::vector<std::string> *set = nullptr; // a set of patterns in place of the one
         std::vector<uint64_t> *hits = nullptr;         // ... and its per-pattern sums over all handles
         const LineSelect *select = nullptr;            // lines: the selected lines in place of the matching ones
+        bool matches = false;                          // lines: the matches of the matching lines in place of the lines (rec_cap is theirs)
+        size_t line_cap = 0;                           // ... and the lines that may take part; per handle where share_line_cap says so
+        const std::vector<size_t> *share_line_cap = nullptr;
     };
+    static void check_regex_ends(const std::string &regex, bool icase)
+    {
+        char msg[256];
+        const int rc = zarc_gpu_regex_compile_ends(regex.data(), regex.size(), icase ? (unsigned)ZARC_GPU_SEARCH_ICASE : 0u, nullptr, msg, sizeof msg);
+        if (rc != ZARC_GPU_OK) throw Error(rc, msg);
+    }
     static void check_regex(const std::string &regex, bool icase)
     {
         char msg[256];
@@ -571,26 +639,36 @@ class FrameReader {
             }
             // lines: no frame holds more matching lines than it has room for matches, so a share's records never need more than this -- and
             // neither does its text buffer, which the call wants rec_cap * max_line bytes large (never touched beyond what is delivered)
-            std::vector<uint64_t> nlines, nselected;
+            std::vector<uint64_t> nlines, nselected, nmatches;
             std::vector<zarc_gpu_line> rec;
+            std::vector<zarc_gpu_match> mrec;
             std::unique_ptr<uint8_t, void (*)(void *)> text(nullptr, std::free);
             size_t rec_cap = 0, rec_used = 0, text_used = 0;
             if (search && search->lines) {
                 uint64_t room = 0;
                 for (size_t j = 0; j < m; j++) room += (search->select ? ul[j] : ul[j] / shortest) + 1; // (selected: no frame has more lines than bytes)
                 rec_cap = (size_t)std::min<uint64_t>(search->rec_cap, room);
-                nlines.resize(m); nselected.resize(m); rec.resize(rec_cap);
+                nlines.resize(m); nselected.resize(m); nmatches.resize(m);
+                if (search->matches) mrec.resize(rec_cap); else rec.resize(rec_cap); // (matches do not overlap: no frame has more than bytes / shortest)
                 text.reset((uint8_t *)std::malloc(std::max<size_t>(1, rec_cap * (size_t)search->max_line)));
                 if (!text) { rc[d] = ZARC_GPU_E_NOMEM; return; }
             }
             zarc_gpu_matcher mt{ZARC_GPU_MATCH_FIXED, search ? search->flags : 0u, nullptr, 0, nullptr};
             zarc_gpu_line_select ls{0, 0, 0, 0};
-            if (search && search->select) {
+            if (search && (search->select || search->matches)) {
                 if (search->set) { mt.kind = ZARC_GPU_MATCH_SET; mt.set = &pset; }
                 else { mt.kind = search->regex ? ZARC_GPU_MATCH_REGEX : ZARC_GPU_MATCH_FIXED; mt.text = search->pattern->data(); mt.text_len = search->pattern->size(); }
+            }
+            if (search && search->select) {
                 ls = zarc_gpu_line_select{search->select->invert ? (uint32_t)ZARC_GPU_SELECT_INVERT : 0u, search->select->before, search->select->after, 0};
             }
-            rc[d] = search && search->lines && search->select
+            rc[d] = search && search->matches
+                        ? zarc_gpu_search_matches_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), &mt,
+                                                        search->max_lines, search->max_line, search->share_line_cap ? (*search->share_line_cap)[d] : search->line_cap,
+                                                        (uint8_t(*)[32])got.data(), status.data(), count.data(), first.data(), search->set ? which.data() : nullptr,
+                                                        search->set ? share_hits[d].data() : nullptr, nlines.data(), nmatches.data(), mrec.data(), rec_cap, &rec_used,
+                                                        text.get(), rec_cap * (size_t)search->max_line, &text_used)
+                    : search && search->lines && search->select
                         ? zarc_gpu_select_lines_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), &mt, &ls,
                                                       search->max_lines, search->max_line, (uint8_t(*)[32])got.data(), status.data(), count.data(), first.data(),
                                                       search->set ? which.data() : nullptr, search->set ? share_hits[d].data() : nullptr, nlines.data(),
@@ -635,8 +713,14 @@ class FrameReader {
                 if (search) { r.count = count[j]; if (first[j] != ZARC_GPU_SEARCH_NONE) r.first = first[j]; }
                 if (search && search->set && which[j] != ZARC_GPU_SEARCH_NONE) r.which = which[j];
                 if (search && search->lines) { r.lines = nlines[j]; r.selected = search->select ? nselected[j] : nlines[j]; }
+                if (search && search->matches) r.matches = nmatches[j];
             }
-            for (size_t k = 0; k < rec_used; k++) {
+            for (size_t k = 0; search && search->matches && k < rec_used; k++) {
+                const zarc_gpu_match &x = mrec[k];
+                out[idx[x.frame]].match_records.push_back(Result::Match{x.start, x.length, x.number, x.line_start, x.which,
+                                                                        std::vector<uint8_t>(text.get() + x.text_off, text.get() + x.text_off + x.text_len)});
+            }
+            for (size_t k = 0; !(search && search->matches) && k < rec_used; k++) {
                 const zarc_gpu_line &l = rec[k];
                 out[idx[l.frame]].line_records.push_back(Result::Line{l.start, l.length, l.number, l.match, std::vector<uint8_t>(text.get() + l.text_off, text.get() + l.text_off + l.text_len)});
             }
