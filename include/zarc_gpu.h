@@ -120,8 +120,14 @@ enum {
                                         block whose pieces would cost more than one raw block goes out as one).  Store mode ignores it.  Other values:
                                         ZARC_GPU_E_PARAM. */
     /* ... and this one changes no byte again, only the time a pack call takes */
-    ZARC_GPU_PX_CHECK_FRAMES = 9008  /* 0 (default) / 1; other values ZARC_GPU_E_PARAM.  1: every pack call decodes its own frames again and compares them
+    ZARC_GPU_PX_CHECK_FRAMES = 9008, /* 0 (default) / 1; other values ZARC_GPU_E_PARAM.  1: every pack call decodes its own frames again and compares them
                                         with the sources before it returns ("read-back check" below) */
+    ZARC_GPU_PX_SEQ_STATES = 9009    /* like ZARC_GPU_PX_DEC_GROUPS it changes no byte.  Pack, frames of several blocks: 1 (default) = the FSE state chains
+                                        of the blocks of a 1 MiB group that code their sequences with the same tables run side by side on one wave, in
+                                        front of the pass that writes the sequences sections; 0 = every block's wave runs its own chains (as before);
+                                        N > 1 = as 1, but only for blocks of fewer than N sequences (for tests and comparisons: the way to reach with small
+                                        inputs what a block too large for its state slot does).  Negative: ZARC_GPU_E_PARAM.  Ignored with
+                                        ZARC_GPU_PX_BLOCK_SPLIT on. */
 };
 /* What the engine does with the libzstd ids (pack.rs:86-217 forwards them all):
  *   CompressionLevel  -131072..22 accepted; four finders (zarc_gpu_level_finder says which one a level runs):

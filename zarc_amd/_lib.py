@@ -29,6 +29,9 @@ PX_SCRATCH_MB, PX_STAGE_CHUNK, PX_STAGE_THREAD, PX_COPY_THREADS, PX_DEC_GROUPS, 
 PX_BLOCK_SPLIT = 9007
 # read-back check of pack: 1 = every frame of a pack call is decoded again and compared with its source before the call returns (default 0)
 PX_CHECK_FRAMES = 9008
+# pack: 1 (default) = the FSE state chains of blocks that share their tables run on one wave per 1 MiB group; 0 = per block; N > 1 = as 1
+# for blocks of fewer than N sequences.  Frames are identical for every value
+PX_SEQ_STATES = 9009
 # zarc_gpu_last_copy_bytes: content bytes the most recent batch call moved over PCIe
 C_H2D, C_D2H, C_RING, C_DIRECT = range(4)
 # timers

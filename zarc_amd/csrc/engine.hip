@@ -109,6 +109,7 @@ struct zarc_gpu {
     DevBuf d_chk_off;           // read-back check: the decoder's output offsets (pack keeps d_dst_off for its later sub-batches)
     DevBuf d_chk_order, d_chk_slices, d_chk_bad; // zarc_check_compare: entry of every sorted frame, slice prefix, first differing byte
     int check_frames = 0;       // ZARC_GPU_PX_CHECK_FRAMES
+    int seq_states = 1;         // ZARC_GPU_PX_SEQ_STATES: 0 = off, 1 = on, N > 1 = on with at most N state words per block
     size_t chk_index = 0;       // the first entry that failed the check in the most recent pack pass, and where (ZARC_CHECK_TRAILER: its trailer)
     uint32_t chk_at = 0;
     float chk_ms = 0;           // zarc_check_compare of the most recent pack pass (diagnostic build prints it)
@@ -498,6 +499,7 @@ int zarc_gpu_set_parameter(zarc_gpu_t *h, int id, int value)
     case ZARC_GPU_PX_ZERO_COPY: if (value < 0 || value > (1 << 20)) return ZARC_GPU_E_PARAM; h->zero_copy = value; return ZARC_GPU_OK;
     case ZARC_GPU_PX_BLOCK_SPLIT: if (value != 0 && value != 1) return ZARC_GPU_E_PARAM; h->block_split = value; return ZARC_GPU_OK;
     case ZARC_GPU_PX_CHECK_FRAMES: if (value != 0 && value != 1) return ZARC_GPU_E_PARAM; h->check_frames = value; return ZARC_GPU_OK;
+    case ZARC_GPU_PX_SEQ_STATES: if (value < 0) return ZARC_GPU_E_PARAM; h->seq_states = value; return ZARC_GPU_OK;
     case ZARC_GPU_P_CONTENT_SIZE_FLAG:
         if (value != 1) return ZARC_GPU_E_UNSUPPORTED; // frames always carry their content size
         return ZARC_GPU_OK;
@@ -935,10 +937,12 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
                                        h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof, h->d_zpieces.as<ZgePiece>());
             } else if (bp[1] - bp[0] > 1) {
                 // the sub-batch holds frames of several blocks (the largest comes first): the entropy stage runs in two passes around the
-                // table plan, which lets the blocks of a group share their sequence tables (zge_entropy.hip: zarc_zge_plan).  (Pass 2 on
-                // its own is bound by LDS instruction issue -- 18.7 ms where its share of the one-pass kernel was 13.7 -- and neither running
-                // pass 1 of one half of the blocks beside pass 2 of the other nor moving the digest kernels beside pass 2 gave any of that
-                // back: tools/r4_ab5.sh, r4_ab7.sh, EXPERIMENTS.md.)
+                // table plan, which lets the blocks of a group share their sequence tables (zge_entropy.hip: zarc_zge_plan).  (Neither
+                // running pass 1 of one half of the blocks beside pass 2 of the other nor moving the digest kernels beside pass 2 gave any
+                // time back: tools/r4_ab5.sh, r4_ab7.sh, EXPERIMENTS.md.  What pass 2 spends is the latency of its FSE state chains, three
+                // lanes of a wave: 9.0 of its 13.0 ms at configs[1] go when they are taken out, 9.5 with the table build, EXPERIMENTS.md
+                // round 18.  With ZARC_GPU_PX_SEQ_STATES on, zarc_zge_seq_states runs the chains of the blocks of a group that share their
+                // tables on one wave in front of pass 2, which then has neither chain nor table build for those blocks.)
                 ZHIP(h->d_plan.reserve(nb * sizeof(ZgePlan)));
                 std::vector<uint32_t> groups; // first block slot of every group of a frame with more than one block (frames come largest first)
                 for (size_t j = 0; j < m && bp[j + 1] - bp[j] > 1; j++)
@@ -948,6 +952,12 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
                                    h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof, h->d_plan.as<ZgePlan>());
                 hipLaunchKernelGGL(zarc_zge_plan, dim3((unsigned)groups.size()), dim3(64), 0, h->stream, (uint32_t)nb, h->d_blocks.as<ZgeBlock>(), h->d_plan.as<ZgePlan>(),
                                    h->d_groups.as<uint32_t>());
+                if (h->seq_states) { // the literal slots are free from here on: a block's states go where its literals were
+                    uint32_t cap_words = (uint32_t)(zge_lit_stride(slot) / 4);
+                    if (h->seq_states > 1) cap_words = std::min<uint32_t>(cap_words, (uint32_t)h->seq_states);
+                    hipLaunchKernelGGL(zarc_zge_seq_states, dim3((unsigned)groups.size()), dim3(64), 0, h->stream, (uint32_t)nb, slot, h->d_blocks.as<ZgeBlock>(),
+                                       h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_plan.as<ZgePlan>(), h->d_groups.as<uint32_t>(), cap_words, eprof);
+                }
                 hipLaunchKernelGGL(zarc_zge_entropy_p2, dim3((unsigned)nb), dim3(64), 0, h->stream, (uint32_t)nb, slot, h->d_blocks.as<ZgeBlock>(),
                                    h->d_seq.as<uint64_t>(), h->d_lit.as<uint8_t>(), h->d_out.as<uint8_t>(), eprof, h->d_plan.as<ZgePlan>(), h->d_enc_err.as<uint32_t>());
             } else
@@ -979,11 +989,12 @@ int pack_device_impl(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint
             fprintf(stderr, "zge_match stage ticks (%% of %llu):", tot);
             for (int i = 0; i < 15; i++) fprintf(stderr, " %d:%.1f", i, tot ? 100.0 * (double)prof[i] / (double)tot : 0.0);
             fprintf(stderr, "\n");
-            ZHIP(hipMemcpy(prof, (const char *)h->d_queue.p + 128, 6 * 8, hipMemcpyDeviceToHost));
+            ZHIP(hipMemcpy(prof, (const char *)h->d_queue.p + 128, 8 * 8, hipMemcpyDeviceToHost)); // [6]: zarc_zge_seq_states, all of a wave's ticks; [7]: blocks it took
             tot = 0;
-            for (int i = 0; i < 6; i++) tot += prof[i];
-            fprintf(stderr, "zge_entropy stage ticks (%% of %llu): hist %.1f huf-build %.1f lit-encode %.1f seq-prepass %.1f seq-tables %.1f seq-encode %.1f\n", tot,
-                    100.0 * prof[0] / tot, 100.0 * prof[1] / tot, 100.0 * prof[2] / tot, 100.0 * prof[3] / tot, 100.0 * prof[4] / tot, 100.0 * prof[5] / tot);
+            for (int i = 0; i < 7; i++) tot += prof[i];
+            fprintf(stderr, "zge_entropy stage ticks (%% of %llu): hist %.1f huf-build %.1f lit-encode %.1f seq-prepass %.1f seq-tables %.1f seq-encode %.1f seq-states %.1f; seq-states blocks %llu\n", tot,
+                    100.0 * prof[0] / tot, 100.0 * prof[1] / tot, 100.0 * prof[2] / tot, 100.0 * prof[3] / tot, 100.0 * prof[4] / tot, 100.0 * prof[5] / tot,
+                    100.0 * prof[6] / tot, prof[7]);
         }
         ms_match += elapsed(h, a, b);
         ms_ent += elapsed(h, b, c);

@@ -60,9 +60,12 @@ struct ZgePlan {
     uint32_t lsz;        // bytes of the literals section in front
     uint32_t extra_bits; // bits of all extra-bits fields (for the size bound)
     uint32_t guaranteed; // zarc_zge_plan: an upper bound of the coded size is below the raw size
-    uint32_t pad[3];
+    uint32_t states;     // zarc_zge_seq_states: 1 = the block's FSE states lie in its literal slot, pass 2 runs no chain (cleared by pass 1)
+    uint32_t pad[2];
     ZgePlanTable t[3];   // LL, OF, ML
 };
+// zarc_zge_seq_states takes the chains of a run of blocks that code with the same tables, if the run has at least this many blocks
+constexpr uint32_t ZGE_STATE_MIN_RUN = 4;
 static_assert(sizeof(ZgePlanTable) == 476 && sizeof(ZgePlan) == 32 + 3 * 476, "plan record layout");
 // Block splitting (ZARC_GPU_PX_BLOCK_SPLIT, off by default; zge_split.hip, model: tests/support/split_model.c).  A 64 KiB parent block
 // becomes up to ZGE_SPLIT_K pieces = Zstandard blocks, cut at sequence boundaries where the literal statistics change.  Every parent
@@ -349,6 +352,10 @@ __global__ void zarc_zge_entropy(uint32_t n_blocks, uint32_t slot_bytes, ZgeBloc
 __global__ void zarc_zge_entropy_p1(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *blocks, uint64_t *seq_scratch, const uint8_t *lit_scratch,
                                     uint8_t *out_scratch, unsigned long long *prof, ZgePlan *plans);
 __global__ void zarc_zge_plan(uint32_t n_blocks, const ZgeBlock *blocks, ZgePlan *plans, const uint32_t *group_start);
+// between the plan and pass 2 (ZARC_GPU_PX_SEQ_STATES): a wave per group runs the FSE state chains of the blocks that code with the same
+// tables side by side and leaves their states in the blocks' literal slots (`cap_words` of a slot may be used); pass 2 then runs no chain
+__global__ void zarc_zge_seq_states(uint32_t n_blocks, uint32_t slot_bytes, const ZgeBlock *blocks, const uint64_t *seq_scratch, uint8_t *lit_scratch,
+                                    ZgePlan *plans, const uint32_t *group_start, uint32_t cap_words, unsigned long long *prof);
 // (*err |= 1 when a block the plan `guaranteed` to end up compressed did not: its successor may repeat tables the decoder never saw)
 __global__ void zarc_zge_entropy_p2(uint32_t n_blocks, uint32_t slot_bytes, ZgeBlock *blocks, uint64_t *seq_scratch, const uint8_t *lit_scratch,
                                     uint8_t *out_scratch, unsigned long long *prof, ZgePlan *plans, uint32_t *err);

@@ -175,6 +175,16 @@ __device__ void fse_build_ctab(FseCtab &t, const int16_t *norm, int nsym, int al
     }
     t.al = al;
 }
+// dnb of a symbol with normalised count n in a table of accuracy `al`: (bits of the larger transition << 16) - the first state that takes
+// them.  It depends on (n, al) alone, so a coder that is handed its states (zarc_zge_seq_states) needs no more than this of a table.
+__device__ __forceinline__ int32_t fse_sym_dnb(int n, int al)
+{
+    const int T = 1 << al;
+    if (n == 0) return ((al + 1) << 16) - T;
+    if (n == -1 || n == 1) return (al << 16) - T;
+    const int max_bits_out = al - zd::hb32((uint32_t)(n - 1));
+    return (max_bits_out << 16) - (n << max_bits_out);
+}
 // The same table built by the whole wave (uniform call; norm[] / nsym / al as above, `cellsym` >= 2^al bytes of LDS scratch):
 //   starts      an exclusive prefix sum of the symbols' cell counts (a "less than one" symbol, norm -1, has one cell)
 //   spread      the j-th visited position is (j * step) mod T, positions above `high` (the less-than-one symbols' cells at the top) are
@@ -644,6 +654,11 @@ __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, u
     uint8_t *out = out_scratch + (uint64_t)slot_i * zge_out_stride(slot_bytes) + (SPLIT ? pieces[bi].out_off : 0u);
     const uint32_t out_cap = SPLIT ? pieces[bi].out_cap : (uint32_t)zge_out_stride(slot_bytes);
     bool fail = false;
+    // pass 2 of whole blocks: zarc_zge_seq_states may have run this block's state chains already (plan->states) and left their states
+    // in the block's literal slot, which nothing reads once pass 1 has coded the literals section
+    constexpr bool STATES = PHASE == 2 && !SPLIT;
+    const bool given = STATES && plan->states != 0;
+    const uint32_t *const swords = (const uint32_t *)(lit_scratch + (uint64_t)slot_i * zge_lit_stride(slot_bytes));
 
     // ================= literals section =================
     uint32_t lsz = PHASE == 2 ? plan->lsz : 0u;
@@ -915,7 +930,7 @@ __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, u
                 if (lane < 53) xb += L.s.cm[lane] * ml_code_bits((uint32_t)lane);
                 if (lane < 32) xb += L.s.co[lane] * (uint32_t)lane;
                 xb = zd::wave_sum(xb);
-                if (lane == 0) { plan->active = 1; plan->nseq = nseq; plan->lsz = lsz; plan->extra_bits = xb; plan->guaranteed = 0; }
+                if (lane == 0) { plan->active = 1; plan->nseq = nseq; plan->lsz = lsz; plan->extra_bits = xb; plan->guaranteed = 0; if (!SPLIT) plan->states = 0; }
             }
             return; // pass 2 goes on from here
           }
@@ -940,7 +955,9 @@ __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, u
                 FseCtab tt = which == 0 ? FseCtab{L.s.st + ST_LL, L.s.dnb_ll, L.s.dfs_ll, 0}
                                         : (which == 1 ? FseCtab{L.s.st + ST_OF, L.s.dnb_of, L.s.dfs_of, 0} : FseCtab{L.s.st + ST_ML, L.s.dnb_ml, L.s.dfs_ml, 0});
                 uint8_t *cells = (uint8_t *)L.s.pre; // 512 bytes of scratch, idle until the chains
-                if (L.ctrl[X_MODE_L + which] != 1) fse_build_ctab_wave(tt, L.s.norm[which], L.ctrl[X_NSYM_L + which], L.ctrl[X_AL_L + which], cells, lane);
+                if (STATES && given) { // the states are given: only the bit counts are left to work out, and they need dnb[] alone
+                    if (L.ctrl[X_MODE_L + which] != 1 && lane < L.ctrl[X_NSYM_L + which]) tt.dnb[lane] = fse_sym_dnb(L.s.norm[which][lane], L.ctrl[X_AL_L + which]);
+                } else if (L.ctrl[X_MODE_L + which] != 1) fse_build_ctab_wave(tt, L.s.norm[which], L.ctrl[X_NSYM_L + which], L.ctrl[X_AL_L + which], cells, lane);
 #ifdef ZGE_DEBUG_FSE
                 if (L.ctrl[X_MODE_L + which] != 1 && lane == 0) {
                     static thread_local uint16_t st2[512]; static thread_local int32_t dnb2[64], dfs2[64]; static thread_local uint8_t cs2[512];
@@ -977,30 +994,37 @@ __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, u
                 WavePacker pk;
                 pk.begin(L.stage, so + pos, scap - pos, lane);
                 uint64_t s_next = (uint32_t)lane < nseq ? seq[nseq - 1 - (uint32_t)lane] : 0;
+                // given states (zarc_zge_seq_states): one word per sequence, LL | OF << 10 | ML << 20 = the state each chain had in front of
+                // that sequence's step, and behind the last one the states the chains ended in; requested a round ahead like the sequences
+                uint32_t w_next = STATES && given && (uint32_t)lane < nseq ? swords[nseq - 1 - (uint32_t)lane] : 0u;
                 for (uint32_t done = 0; done < nseq; done += 64) {
                     const uint32_t cnt = nseq - done < 64 ? nseq - done : 64;
                     // element e of this round is sequence index (nseq-1-done-e); lane e classifies it (requested a round ahead)
                     uint32_t ll = 0, ml = 3, ofv = 1, llc = 0, mlc = 0, ofc = 0;
                     const uint64_t s = s_next;
+                    const uint32_t w = w_next;
                     if (done + 64 + (uint32_t)lane < nseq) s_next = seq[nseq - 1 - done - 64 - (uint32_t)lane];
+                    if (STATES && given && done + 64 + (uint32_t)lane < nseq) w_next = swords[nseq - 1 - done - 64 - (uint32_t)lane];
                     if ((uint32_t)lane < cnt) {
                         ll = zge_seq_ll(s); ml = zge_seq_ml(s); ofv = zge_seq_ofv(s);
                         llc = ll_code(ll); mlc = ml_code(ml); ofc = (uint32_t)zd::hb32(ofv);
+                      if (!(STATES && given)) {
                         // per-symbol transition constants fetched by all lanes at once: the serial loop below then has a
                         // single dependent LDS access per step (the state table)
                         L.s.pre[0][lane] = (uint32_t)L.s.dnb_ll[llc] | ((uint64_t)(uint32_t)(2 * (L.s.dfs_ll[llc] + ST_LL)) << 32); // byte offset into st[]
                         L.s.pre[1][lane] = (uint32_t)L.s.dnb_of[ofc] | ((uint64_t)(uint32_t)(2 * (L.s.dfs_of[ofc] + ST_OF)) << 32);
                         L.s.pre[2][lane] = (uint32_t)L.s.dnb_ml[mlc] | ((uint64_t)(uint32_t)(2 * (L.s.dfs_ml[mlc] + ST_ML)) << 32);
+                      }
                     }
                     zd::wave_sync();
-                    if (lane < 3 && my_mode != 1) {
+                    if (lane < 3 && my_mode != 1 && !(STATES && given)) {
                         // The chain does the bare minimum per step -- remember the state, find the next one (one dependent LDS access);
                         // the bits each step emits follow from (state before, symbol constant) and are worked out by all lanes below.
                         // Four steps per trip: their symbol constants are fetched together and the loop bookkeeping is paid once.
                         uint64_t *const pp = L.s.pre[lane];
                         // the state each step starts from goes to sbp[] (the normalised counts are dead once the tables are built): four
-                        // steps' states in ONE 64-bit store -- the stage is bound by LDS instruction issue, and a store per step was a
-                        // third of the chain's LDS instructions
+                        // steps' states in ONE 64-bit store -- a store per step was a third of the chain's LDS instructions (what bounds the chain
+                        // is the latency of its dependent steps, EXPERIMENTS.md round 18, not LDS issue as was thought when this was written)
                         typedef uint16_t __attribute__((may_alias)) u16a;
                         typedef uint64_t __attribute__((may_alias)) u64a;
                         u16a *const sbp = (u16a *)&L.s.norm[0][0] + 64 * lane;
@@ -1036,7 +1060,13 @@ __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, u
                         // symbol coded and tables in RLE mode emit nothing
                         uint32_t bo = 0, bm = 0, bl = 0;
                         const bool first = done + (uint32_t)lane == 0;
-                        if (!first) {
+                        if (STATES && given) {
+                            if (!first) {
+                                if (mode_o != 1) { const uint32_t c = (uint32_t)L.s.dnb_of[ofc], sb = (w >> 10) & 1023u, n_ = (sb + c) >> 16; bo = (sb & ((1u << n_) - 1)) | (n_ << 16); }
+                                if (mode_m != 1) { const uint32_t c = (uint32_t)L.s.dnb_ml[mlc], sb = w >> 20, n_ = (sb + c) >> 16; bm = (sb & ((1u << n_) - 1)) | (n_ << 16); }
+                                if (mode_l != 1) { const uint32_t c = (uint32_t)L.s.dnb_ll[llc], sb = w & 1023u, n_ = (sb + c) >> 16; bl = (sb & ((1u << n_) - 1)) | (n_ << 16); }
+                            }
+                        } else if (!first) {
                             if (mode_o != 1) { const uint32_t c = (uint32_t)L.s.pre[1][lane], sb = ((const uint16_t __attribute__((may_alias)) *)&L.s.norm[0][0])[1 * 64 + lane], n_ = (sb + c) >> 16; bo = (sb & ((1u << n_) - 1)) | (n_ << 16); }
                             if (mode_m != 1) { const uint32_t c = (uint32_t)L.s.pre[2][lane], sb = ((const uint16_t __attribute__((may_alias)) *)&L.s.norm[0][0])[2 * 64 + lane], n_ = (sb + c) >> 16; bm = (sb & ((1u << n_) - 1)) | (n_ << 16); }
                             if (mode_l != 1) { const uint32_t c = (uint32_t)L.s.pre[0][lane], sb = ((const uint16_t __attribute__((may_alias)) *)&L.s.norm[0][0])[0 * 64 + lane], n_ = (sb + c) >> 16; bl = (sb & ((1u << n_) - 1)) | (n_ << 16); }
@@ -1058,7 +1088,8 @@ __device__ __forceinline__ void zge_entropy_body(EntLds &L, uint32_t n_blocks, u
                 }
                 // flush ML, OF, LL states (in that order)
                 {
-                    const uint32_t st_l = zd::shfl(state, 0), st_o = zd::shfl(state, 1), st_m = zd::shfl(state, 2);
+                    uint32_t st_l = zd::shfl(state, 0), st_o = zd::shfl(state, 1), st_m = zd::shfl(state, 2);
+                    if (STATES && given) { const uint32_t fin = swords[nseq]; st_l = fin & 1023u; st_o = (fin >> 10) & 1023u; st_m = fin >> 20; }
                     uint64_t lo = 0; uint32_t nb = 0;
                     if (lane == 0) {
                         if (mode_m != 1) { lo |= (uint64_t)(st_m & ((1u << al_m) - 1)) << nb; nb += (uint32_t)al_m; }
@@ -1267,6 +1298,186 @@ __global__ void __launch_bounds__(64) zarc_zge_plan_split(uint32_t n_blocks, con
     __shared__ uint8_t gdesc[3][80];
     __shared__ uint32_t gdl[3];
     zge_plan_body<true>(gnorm, gdesc, gdl, n_blocks, blocks, plans, group_start, pblocks);
+}
+
+// The state chains of a table group on one wave (ZARC_GPU_PX_SEQ_STATES; between zarc_zge_plan and pass 2).  In pass 2 a block's three
+// FSE chains are 64 dependent steps per round on lanes 0..2 of the block's wave, and since the plan most blocks of a group code with one
+// set of tables, each of which every wave builds again.  Here one wave per group (the plan's grid) walks the group's blocks in frame
+// order and cuts them into RUNS of blocks that code with the same tables:
+//   a block continues the run of the block in front of it if both are active (pass 2 codes them) and it says Repeat_Mode (3) for every
+//   type it codes with a table, i.e. every type whose mode is not RLE (1).  The plan hands out mode 3 only behind an active block that
+//   codes that type with the group's table, so by induction every table a block of the run uses is the one the run's FIRST block
+//   names in its plan record (norm / al / nsym), and a type the first block has in RLE mode is in RLE mode in the whole run.
+// A run with at least ZGE_STATE_MIN_RUN blocks whose states fit their slots is TAKEN (a group of 16 has four at most): its tables are
+// built once (fse_build_ctab_wave, the code pass 2 uses), block b of the run gets lanes 3b .. 3b + 2 for its LL / OF / ML chains, and
+// the wave goes through rounds of 64 sequences per block, last sequence first, like pass 2: all lanes classify the sequences of each
+// block (requested a round ahead) and post the symbols' constants, the chain lanes take 64 steps (the step of pass 2's CHAIN_NEXT, the
+// first symbol coded taking the state that needs no bits) and leave the state in front of each step where the constant was, all lanes
+// merge the three states of a sequence into one word, LL | OF << 10 | ML << 20 (states are below 2^10: accuracy 9 at most), and
+// store it at the sequence's index in the block's literal slot; word nseq holds the states the chains ended in (what pass 2 flushes).
+// The literal slot is free: pass 1 has coded the literals section from it, pass 2 takes `lsz` from the plan and reads no literal,
+// the assembly pass copies raw blocks from the source, and the read-back check and repack see frames only.  A block with more than
+// cap_words - 1 sequences is not taken (its lanes idle, pass 2 runs its chain), nor is any block of a shorter run.
+// No barrier, no atomics on shared words, no waiting on another wave: every loop is bounded by the group's 16 blocks or a block's
+// sequence count.
+// LDS: 48 rows of constants (68 words: the rows of the 48 chain lanes start 4 banks apart) + one set of tables = 17 968 bytes, so 8
+// waves per CU (the CU's 160 KiB / 17 968, less the allocation granule); 7 500 groups at configs[1] are under four waves per slot.
+namespace {
+constexpr int SS_ROW = 68;
+struct StatesLds {
+    alignas(16) uint32_t pre[3 * ZGE_TABLE_GROUP][SS_ROW]; // row 3b + t: type t (LL, OF, ML) of the run's block b -- the symbol constant of each of the round's sequences, then the state in front of its step
+    uint16_t st[1280];                                     // state tables, laid out like pass 2's
+    int32_t dnb_ll[36], dfs_ll[36], dnb_ml[53], dfs_ml[53], dnb_of[32], dfs_of[32];
+    uint32_t cc_ll[36], cc_of[32], cc_ml[53];              // per symbol: dnb (20 bits) | (dfs + the table's start in st[] + 1024) << 20
+    int16_t norm[3][64];
+    uint8_t cells[512];
+};
+} // namespace
+
+__global__ void __launch_bounds__(64) zarc_zge_seq_states(uint32_t n_blocks, uint32_t slot_bytes, const ZgeBlock *__restrict__ blocks, const uint64_t *__restrict__ seq_scratch,
+                                                          uint8_t *__restrict__ lit_scratch, ZgePlan *__restrict__ plans, const uint32_t *__restrict__ group_start,
+                                                          uint32_t cap_words, unsigned long long *__restrict__ prof /* [6] ticks of all waves, [7] blocks taken (diagnostics) or null */)
+{
+    __shared__ StatesLds S;
+    const int lane = zd::lane_id();
+    const unsigned long long t_start = ZGE_CLOCK();
+    const uint32_t bi = group_start[blockIdx.x];
+    if (bi >= n_blocks) return;
+    const uint32_t frame = blocks[bi].frame, index0 = blocks[bi].index;
+    if (index0 % ZGE_TABLE_GROUP) return;
+    uint32_t nb = 1;
+    while (nb < ZGE_TABLE_GROUP && bi + nb < n_blocks && blocks[bi + nb].frame == frame && blocks[bi + nb].index == index0 + nb) nb++;
+    // lane b < nb looks at block b of the group
+    uint32_t act = 0, nsq = 0, m0 = 1, m1 = 1, m2 = 1;
+    if ((uint32_t)lane < nb) {
+        const ZgePlan *p = plans + bi + lane;
+        act = p->active; nsq = p->nseq; m0 = p->t[0].mode; m1 = p->t[1].mode; m2 = p->t[2].mode;
+    }
+    uint32_t prev_act = zd::shfl_up1(act);
+    if (lane == 0) prev_act = 0;
+    const bool cont = act && prev_act && (m0 == 1 || m0 == 3) && (m1 == 1 || m1 == 3) && (m2 == 1 || m2 == 3); // the run rule above
+    uint64_t heads = zd::ballot(act && !cont);
+    const uint64_t contm = zd::ballot(cont), fits = zd::ballot(act && nsq != 0 && nsq < cap_words);
+    uint32_t *const my_words = (uint32_t *)(lit_scratch + (uint64_t)(bi + ((uint32_t)lane < nb ? (uint32_t)lane : 0u)) * zge_lit_stride(slot_bytes));
+    while (heads) { // at most 16 runs, at most four of them taken
+        const uint32_t h = (uint32_t)zd::ctz64(heads);
+        heads &= heads - 1;
+        const uint32_t R = 1 + (uint32_t)zd::ctz64(~(contm >> (h + 1))); // blocks h .. h + R - 1
+        const uint64_t taken = fits & (((1ull << R) - 1) << h);
+        if ((uint32_t)__popcll(taken) < ZGE_STATE_MIN_RUN) continue;
+        if (prof && lane == 0) atomicAdd(prof + 7, (unsigned long long)__popcll(taken)); // diagnostics: blocks whose states are computed here
+        // ---- the run's tables, from its first block's plan record
+        const ZgePlan *const hp = plans + bi + h;
+        const int hm[3] = {(int)zd::readlane(m0, h), (int)zd::readlane(m1, h), (int)zd::readlane(m2, h)};
+#pragma unroll
+        for (int which = 0; which < 3; which++) S.norm[which][lane] = hp->t[which].norm[lane];
+        zd::wave_sync();
+#pragma unroll
+        for (int which = 0; which < 3; which++) {
+            FseCtab tt = which == 0 ? FseCtab{S.st + ST_LL, S.dnb_ll, S.dfs_ll, 0}
+                                    : (which == 1 ? FseCtab{S.st + ST_OF, S.dnb_of, S.dfs_of, 0} : FseCtab{S.st + ST_ML, S.dnb_ml, S.dfs_ml, 0});
+            const int nsym = hp->t[which].nsym, al = hp->t[which].al, nc = which == 0 ? 36 : (which == 1 ? 32 : 53);
+            uint32_t *const cc = which == 0 ? S.cc_ll : (which == 1 ? S.cc_of : S.cc_ml);
+            const int start = which == 0 ? ST_LL : (which == 1 ? ST_OF : ST_ML);
+            if (hm[which] != 1) fse_build_ctab_wave(tt, S.norm[which], nsym, al, S.cells, lane);
+            // (a symbol the table does not have is never coded; its constant keeps a stray lookup inside st[])
+            if (lane < nc) cc[lane] = hm[which] != 1 && lane < nsym ? (uint32_t)tt.dnb[lane] | ((uint32_t)(tt.dfs[lane] + start + 1024) << 20) : 1024u << 20;
+            zd::wave_sync();
+        }
+        // ---- this lane's chain: type lane % 3 of block h + lane / 3
+        const uint32_t cb = h + (uint32_t)lane / 3u, ct = (uint32_t)lane % 3u;
+        const uint32_t cb_c = cb < ZGE_TABLE_GROUP ? cb : 0u;
+        const uint32_t c_nseq = zd::shfl(nsq, (int)cb_c);
+        const uint32_t c_m0 = zd::shfl(m0, (int)cb_c), c_m1 = zd::shfl(m1, (int)cb_c), c_m2 = zd::shfl(m2, (int)cb_c);
+        const bool chain = (uint32_t)lane < 3 * R && ((taken >> cb_c) & 1) && (ct == 0 ? c_m0 : (ct == 1 ? c_m1 : c_m2)) != 1;
+        uint32_t state = 0;
+        const uint32_t maxn = zd::uniform(zd::wave_max(((taken >> lane) & 1) ? nsq : 0u));
+        // The sequences of each block's round live in sixteen scalars, sv0 .. sv15, requested a round ahead: the loads of the next round
+        // go out in front of the chain steps and are waited for behind them.  (An array here becomes one 32-register tuple that is
+        // copied as a whole around every load, each load waited for at once: the kernel then took 7.3 ms at configs[1].)  Every lane
+        // loads -- past a block's sequences it asks for sequence 0 again -- so the loads stand outside any branch on the lane.
+#define SS_EACH(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15)
+        // (a request of a block that is not of the run, or not taken, asks for sequence 0 of the run's first block: straight-line code)
+#define SS_LOAD(r, at) { const bool on = (r) < R && ((taken >> (h + (r))) & 1); const uint32_t nr = on ? zd::readlane(nsq, h + (r)) : 0u, rb = on ? (r) : 0u;          \
+                         sv##r = seq_scratch[(uint64_t)(bi + h + rb) * zge_seq_stride(slot_bytes) + ((at) + (uint32_t)lane < nr ? nr - 1 - (at) - (uint32_t)lane : 0u)]; }
+#define SS_FIRST(r) uint64_t sv##r; SS_LOAD(r, 0u)
+        SS_EACH(SS_FIRST)
+#undef SS_FIRST
+        for (uint32_t done = 0; done < maxn; done += 64) {
+            // element e of a block's round is its sequence nseq - 1 - done - e; lane e classifies it and posts the constants
+#define SS_POST(r) if ((r) < R && ((taken >> (h + (r))) & 1)) {                                                                                  \
+                const uint32_t nr = zd::readlane(nsq, h + (r));                                                                                 \
+                if (done < nr) {                                                                                                                \
+                    const uint64_t s = sv##r;                                                                                                   \
+                    if (done + (uint32_t)lane < nr) {                                                                                           \
+                        S.pre[3 * (r) + 0][lane] = S.cc_ll[ll_code(zge_seq_ll(s))];                                                             \
+                        S.pre[3 * (r) + 1][lane] = S.cc_of[zd::hb32(zge_seq_ofv(s))];                                                           \
+                        S.pre[3 * (r) + 2][lane] = S.cc_ml[ml_code(zge_seq_ml(s))];                                                             \
+                    } } }
+            SS_EACH(SS_POST)
+#undef SS_POST
+            // the next round's requests, all behind the posts and with no branch between them: behind a branch the compiler counts the
+            // outstanding loads conservatively and waits for the request in front before it issues the next one
+#define SS_AHEAD(r) SS_LOAD(r, done + 64)
+            SS_EACH(SS_AHEAD)
+#undef SS_AHEAD
+            zd::wave_sync();
+            if (chain && done < c_nseq) {
+                const uint32_t cnt = c_nseq - done < 64 ? c_nseq - done : 64;
+                uint32_t *const pp = S.pre[lane];
+                uint32_t e = 0;
+                if (done == 0) { // first symbol coded: the state that needs no bits (fse_init_state)
+                    const uint32_t c0 = pp[0];
+                    const int32_t d = (int32_t)(c0 & 0xFFFFFu);
+                    const int nb0 = (d + (1 << 15)) >> 16;
+                    const int value = (nb0 << 16) - d;
+                    state = *(const uint16_t *)((const uint8_t *)S.st + 2 * ((uint32_t)(value >> nb0) + (c0 >> 20)) - 2048);
+                    pp[0] = 0; // no state in front of it
+                    e = 1;
+                }
+                // one step: the state table's start and the bias of 1024 are part of the constant
+#define STATE_NEXT(cur) do { const uint32_t nb_ = (state + ((cur) & 0xFFFFFu)) >> 16;                                      \
+                             state = *(const uint16_t *)((const uint8_t *)S.st + 2 * ((state >> nb_) + ((cur) >> 20)) - 2048); } while (0)
+                for (; (e & 3u) && e < cnt; e++) { const uint32_t c0 = pp[e]; pp[e] = state; STATE_NEXT(c0); }
+                for (; e + 4 <= cnt; e += 4) { // four constants in one load, four states in one store
+                    uint32_t c4[4], o4[4];
+                    __builtin_memcpy(c4, __builtin_assume_aligned(pp + e, 16), 16);
+                    o4[0] = state; STATE_NEXT(c4[0]);
+                    o4[1] = state; STATE_NEXT(c4[1]);
+                    o4[2] = state; STATE_NEXT(c4[2]);
+                    o4[3] = state; STATE_NEXT(c4[3]);
+                    __builtin_memcpy(__builtin_assume_aligned(pp + e, 16), o4, 16);
+                }
+                for (; e < cnt; e++) { const uint32_t c0 = pp[e]; pp[e] = state; STATE_NEXT(c0); }
+#undef STATE_NEXT
+            }
+            zd::wave_sync();
+            // the three states in front of each sequence's step -> one word at the sequence's index
+#define SS_MERGE(r) if ((r) < R && ((taken >> (h + (r))) & 1)) {                                                                                 \
+                const uint32_t nr = zd::readlane(nsq, h + (r));                                                                                 \
+                if (done < nr) {                                                                                                                \
+                    const uint32_t k0 = zd::readlane(m0, h + (r)) != 1 ? 1023u : 0u, k1 = zd::readlane(m1, h + (r)) != 1 ? 1023u : 0u,           \
+                                   k2 = zd::readlane(m2, h + (r)) != 1 ? 1023u : 0u;                                                             \
+                    uint32_t *const words = (uint32_t *)(lit_scratch + (uint64_t)(bi + h + (r)) * zge_lit_stride(slot_bytes));                   \
+                    if (done + (uint32_t)lane < nr)                                                                                             \
+                        words[nr - 1 - done - (uint32_t)lane] = (S.pre[3 * (r) + 0][lane] & k0) | ((S.pre[3 * (r) + 1][lane] & k1) << 10) |     \
+                                                                 ((S.pre[3 * (r) + 2][lane] & k2) << 20);                                        \
+                } }
+            SS_EACH(SS_MERGE)
+#undef SS_MERGE
+            zd::wave_sync();
+        }
+#undef SS_LOAD
+#undef SS_EACH
+        // ---- the states the chains ended in, and the flag: lane b for block b
+        {
+            const uint32_t rr = (uint32_t)lane >= h && (uint32_t)lane < h + R ? (uint32_t)lane - h : 0u;
+            const uint32_t fin = zd::shfl(state, (int)(3 * rr)) | (zd::shfl(state, (int)(3 * rr + 1)) << 10) | (zd::shfl(state, (int)(3 * rr + 2)) << 20);
+            if ((taken >> lane) & 1) { my_words[nsq] = fin; plans[bi + lane].states = 1; }
+        }
+        zd::wave_sync();
+    }
+    if (prof && lane == 0) atomicAdd(prof + 6, ZGE_CLOCK() - t_start);
 }
 
 // the cut decision of ZARC_GPU_PX_BLOCK_SPLIT (zarc_zge_split): same translation unit, see the note at its top
