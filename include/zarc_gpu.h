@@ -48,7 +48,8 @@ extern "C" {
                                   zarc_gpu_search_lines_batch* with ZARC_GPU_T_LINES after those (ZARC_GPU_T_COUNT grew from 11 to 12), then
                                   zarc_gpu_search_set_*, and zarc_gpu_regex_compile with zarc_gpu_search_regex_* (new symbols; ZARC_GPU_T_COUNT stays 12), then
                                   zarc_gpu_select_lines_batch* (new symbols and types; nothing existing changes), then zarc_gpu_search_matches_batch* with
-                                  zarc_gpu_regex_compile_ends and zarc_gpu_match (the same: new symbols and one new type) */
+                                  zarc_gpu_regex_compile_ends and zarc_gpu_match (the same: new symbols and one new type), then
+                                  zarc_gpu_read_ranges_batch* with ZARC_GPU_T_RANGE (new symbols and types; ZARC_GPU_T_COUNT grew from 12 to 13) */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -601,6 +602,54 @@ int zarc_gpu_search_matches_batch_device(zarc_gpu_t *h, size_t n, const void *d_
                                          uint64_t *matches, zarc_gpu_match *rec /* HOST array */, size_t rec_cap, size_t *rec_used,
                                          void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
 
+/* ---- read ranges: byte and line ranges of frames, cut out on the device ------------------------------------------------------------------ */
+/* What `tar -xO file | head -n N` (tail, sed -n 'A,Bp', head -c, tail -c) answers, for a batch of frames: every frame is decoded and judged as
+ * zarc_gpu_verify_batch does it, one range of its content is found where the decoded bytes lie, and only that range's bytes leave the
+ * device.  range[i] (HOST memory in every form) names the range of frame i in UNITS that tile the frame's content exactly:
+ *   - ZARC_GPU_RANGE_BYTES: every byte is a unit; T = raw_len[i].
+ *   - ZARC_GPU_RANGE_LINES: a unit is a line together with its 0x0A; T = the number of 0x0A bytes, + 1 if the content is non-empty and its
+ *     last byte is not 0x0A.  An empty frame has T = 0, "\n" has T = 1, a 0x0D stays an ordinary byte.  This is the line of
+ *     zarc_gpu_search_lines_batch plus its terminator, so consecutive ranges concatenate to the content.
+ *   - The range [a, b) of units.  Without ZARC_GPU_RANGE_FROM_END: a = min(skip, T), b = min(a + take, T).  With it: b = T - min(skip, T),
+ *     a = b - min(take, b).  Every sum saturates; any skip and take are legal; take == ZARC_GPU_RANGE_ALL means "to the end" without the
+ *     flag and "from the beginning" with it.  head -n N: skip 0, take N.  head -n -N: FROM_END, skip N, take ALL.  tail -n N: FROM_END,
+ *     skip 0, take N.  tail -n +K: skip K - 1, take ALL.  sed -n 'A,Bp': skip A - 1, take B - A + 1.  head -c / tail -c: the same, BYTES.
+ *   - res[i]: units = T, first = a, taken = b - a, start = the offset of unit a's first byte in the content (raw_len[i] when a == T),
+ *     length = the bytes of units a .. b - 1 (0 when a == b).  These five are the truth whatever the caps.  reserved = 0.
+ *   - status[i] and digest[i] are EXACTLY what zarc_gpu_verify_batch gives for the same frame and `expect`.  A frame takes part when it
+ *     decoded: ZARC_GPU_FRAME_OK, and ZARC_GPU_FRAME_DIGEST as well.  Every other status: res[i] all zero and no bytes.
+ *   - Delivery, the lines calls' rule with bytes in the place of records: frames in batch order; frame i delivers the first
+ *     e_i = min(length, max_bytes (0 = no limit), text_cap - sum of e_j, j < i) bytes of its range to text + text_off, text_off = the running
+ *     sum, text_len = e_i, *text_used = the sum of all e_i.  A caller sees a cut by text_len < length and fetches the rest with the BYTES
+ *     range {skip = start + text_len, take = length - text_len}.  text_cap == 0 is a counting call: text may be NULL, *text_used is 0.
+ *   - The same frame may stand in a batch several times with different ranges.
+ *   - Checks: zarc_gpu_verify_batch's first, in its order; then, as ZARC_GPU_E_PARAM, a missing range / res / text_used, an unknown unit, an
+ *     unknown flag bit, a NULL text with text_cap > 0.  n == 0: ZARC_GPU_OK, *text_used = 0.  A frame or raw length of 4 GiB or more:
+ *     ZARC_GPU_E_UNSUPPORTED.
+ *   - res, text and *text_used are identical for every ZARC_GPU_PX_SCRATCH_MB, every ZARC_GPU_PX_STAGE_CHUNK, both forms and every number of
+ *     handles a caller deals the batch to: the remainder of text_cap and the text offset are carried from part to part.
+ *   - Host form: `text` is host memory; the frames go up and exactly *text_used bytes of content come back (zarc_gpu_last_copy_bytes:
+ *     H2D = sum of frame_len, D2H = *text_used).  Device form: frames and d_text are device memory, res and every per-frame array are host
+ *     arrays; the counters report 0.
+ *   - zarc_gpu_last_kernel_ms: verify's timers, ZARC_GPU_T_RANGE for zarc_range_* summed over the parts of the call, ZARC_GPU_T_TOTAL
+ *     including it.
+ *   - Cost: decode and both hash passes are verify's and run in full (no early stop inside a frame).  Beside them a BYTES range reads no
+ *     content but what it gathers; a LINES range reads the decoded bytes of its frame once to count 0x0A bytes, plus at most two 64 KiB
+ *     slices to locate its two boundaries, plus what it gathers. */
+enum { ZARC_GPU_RANGE_BYTES = 0, ZARC_GPU_RANGE_LINES = 1 };   /* unit */
+enum { ZARC_GPU_RANGE_FROM_END = 1 };                           /* flags; any other bit: ZARC_GPU_E_PARAM */
+#define ZARC_GPU_RANGE_ALL UINT64_MAX
+typedef struct { uint32_t unit, flags; uint64_t skip, take; } zarc_gpu_range;            /* one per frame, HOST memory */
+typedef struct { uint64_t units, first, taken, start, length, text_off, text_len, reserved; } zarc_gpu_range_result;
+int zarc_gpu_read_ranges_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                               const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const zarc_gpu_range *range /* n */,
+                               uint64_t max_bytes /* per frame; 0 = no limit */, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status,
+                               zarc_gpu_range_result *res /* n */, void *text, size_t text_cap, size_t *text_used);
+int zarc_gpu_read_ranges_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                      const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const zarc_gpu_range *range /* HOST, n */,
+                                      uint64_t max_bytes, uint8_t *digest /* n*32 */, int *status, zarc_gpu_range_result *res /* HOST, n */,
+                                      void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
+
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN]);
@@ -627,7 +676,8 @@ enum {
     ZARC_GPU_T_DEC_FRAMES = 9,/* decoder frame pass (zarc_zstd_frames + the inline decoder for the rest)  */
     ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan (a set: zarc_set_scan and zarc_set_which; a regex: zarc_regex_summary, _carry and _scan), summed over the parts of a call; < 0 or 0 after any other call */
     ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set or a regex: its twins of mark and emit; select_lines: zarc_lines_select_* in place of mark, carry and emit; search_matches: zarc_matches_* behind emit, in place of scan and gather), summed over the parts of a call; < 0 or 0 after any other call */
-    ZARC_GPU_T_COUNT = 12
+    ZARC_GPU_T_RANGE = 12,    /* read_ranges: zarc_range_* (count, carry, locate, gather), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_COUNT = 13
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);
 /* Content bytes the most recent batch call moved between host and device (descriptor arrays, statuses, digests not counted).  Every

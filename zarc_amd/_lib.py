@@ -45,6 +45,9 @@ LINES_MAX_LINE = 65536  # zarc_gpu_search_lines_batch*: the largest max_line
 MATCH_FIXED, MATCH_SET, MATCH_REGEX = 0, 1, 2  # zarc_gpu_select_lines_batch*: zarc_gpu_matcher.kind
 SELECT_INVERT = 1  # ... and zarc_gpu_line_select.flags
 REGEX_MAX_PATTERN, REGEX_MAX_STATES = 1024, 64  # zarc_gpu_search_regex_*: the longest expression, the most states of its automaton
+T_RANGE = 12   # zarc_range_* of a read_ranges call (summed over its parts)
+# zarc_gpu_read_ranges_batch*: zarc_gpu_range.unit, .flags, and the take that means "all the rest"
+RANGE_BYTES, RANGE_LINES, RANGE_FROM_END, RANGE_ALL = 0, 1, 1, 2 ** 64 - 1
 
 EXPORTS = [
     "zarc_gpu_abi_version", "zarc_gpu_level_finder", "zarc_gpu_parameter_advisory", "zarc_gpu_device_count", "zarc_gpu_create", "zarc_gpu_destroy", "zarc_gpu_set_parameter", "zarc_gpu_get_params",
@@ -56,6 +59,7 @@ EXPORTS = [
     "zarc_gpu_regex_compile", "zarc_gpu_search_regex_batch", "zarc_gpu_search_regex_batch_device", "zarc_gpu_search_regex_lines_batch",
     "zarc_gpu_search_regex_lines_batch_device", "zarc_gpu_select_lines_batch", "zarc_gpu_select_lines_batch_device",
     "zarc_gpu_regex_compile_ends", "zarc_gpu_search_matches_batch", "zarc_gpu_search_matches_batch_device",
+    "zarc_gpu_read_ranges_batch", "zarc_gpu_read_ranges_batch_device",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -122,6 +126,16 @@ class MatcherDesc(ctypes.Structure):
 class LineSelect(ctypes.Structure):
     """zarc_gpu_line_select: which lines a select_lines call delivers"""
     _fields_ = [(n, ctypes.c_uint32) for n in ("flags", "before", "after", "reserved")]
+
+
+class Range(ctypes.Structure):
+    """zarc_gpu_range: the range of one frame of a read_ranges call (host memory)"""
+    _fields_ = [("unit", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("skip", ctypes.c_uint64), ("take", ctypes.c_uint64)]
+
+
+class RangeResult(ctypes.Structure):
+    """zarc_gpu_range_result: what a read_ranges call found and delivered of one frame"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("units", "first", "taken", "start", "length", "text_off", "text_len", "reserved")]
 
 
 class RegexDfa(ctypes.Structure):
@@ -206,6 +220,9 @@ def load(path=None):
                                                   vp, sz, szp]
     lib.zarc_gpu_search_matches_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, mp, c.c_uint64, c.c_uint64, sz, vp, ip, u64p, u64p, u64p, u64p, u64p, u64p,
                                                          xp, sz, szp, vp, sz, szp]
+    rp, rrp = c.POINTER(Range), c.POINTER(RangeResult)
+    lib.zarc_gpu_read_ranges_batch.argtypes = [vp, sz, vpp, szp, szp, vp, rp, c.c_uint64, vp, ip, rrp, vp, sz, szp]
+    lib.zarc_gpu_read_ranges_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, rp, c.c_uint64, vp, ip, rrp, vp, sz, szp]
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

@@ -133,6 +133,10 @@ struct zarc_gpu {
     DevBuf d_regex_fwd;                         // the forward table (search_prepare)
     DevBuf d_mt_bitoff, d_mt_bits;              // a regex: first word of every line record's start bits (and the sum); the bits, at most decoded bytes / 8 + 4 per record
     DevBuf d_mt_counts, d_mt_prefix, d_mt_rec;  // matches of every line record; their exclusive sums (and the total); the part's match records
+    // byte and line ranges (zarc_gpu_read_ranges_batch*): zarc_range_* over d_vout behind the verdict of a verify pass, per part
+    DevBuf d_rg_slices, d_rg_req, d_rg_cnt;     // slice prefix; the ranges (decoder order); 0x0A bytes of every slice of a LINES frame
+    DevBuf d_rg_frames, d_rg_open, d_rg_nopen;  // ZarcRangeFrame of every frame (decoder order); the boundaries that wait for zarc_range_locate, and how many
+    DevBuf d_rg_plan, d_rg_blocks, d_rg_text;   // what the host decided: the part's copies and their block prefix; (host form) the part's text
     bool vout_busy = false;     // a repack pass is between its halves: d_vout is not the check's to take
     uint64_t dec_scratch = 0;   // decoder scratch (sequences, literals, tables) of the most recent decode, as counted against the budget
     // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
@@ -697,13 +701,28 @@ SearchReq part_of(SearchReq r, size_t a)
     if (r.lines) { r.ln.lines += a; r.ln.frame0 += a; if (r.ln.selected) r.ln.selected += a; if (r.ln.mt.on) r.ln.mt.matches += a; }
     return r;
 }
+// A verify pass that cuts a range out of what it decoded (zarc_gpu_read_ranges_batch*): zarc_range_* run behind the verdict, per part, while
+// that part's bytes are in d_vout.  The parts of a call are ranges of the caller's frames in the caller's order, so the running sum in `run`
+// gives every frame the same text offset and the same remainder of text_cap however the call is cut.
+struct RangeRun { uint64_t text_used = 0; };
+struct RangeReq {
+    const zarc_gpu_range *range;   // host, in the caller's order, this part's first frame first
+    zarc_gpu_range_result *res;    // host, likewise
+    uint64_t max_bytes;            // per frame; 0 = no limit
+    uint64_t text_cap;             // the call's
+    uint8_t *d_text;               // device form: the caller's text buffer
+    uint8_t *h_text;               // host form: the caller's text buffer (the part's text is gathered into scratch of the handle first)
+    RangeRun *run;
+};
+RangeReq part_of(RangeReq r, size_t a) { r.range += a; r.res += a; return r; }
 int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
+static_assert(sizeof(ZarcRangeReq) == sizeof(zarc_gpu_range), "the device's range is the caller's");
 static_assert(sizeof(ZarcLineRec) == sizeof(zarc_gpu_line), "the device's record is the caller's");
 static_assert(sizeof(ZarcMatchRec) == sizeof(zarc_gpu_match), "the device's record is the caller's");
 
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, void *d_dst_base,
                         const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk,
-                        const SearchReq *srch = nullptr);
+                        const SearchReq *srch = nullptr, const RangeReq *rng = nullptr);
 int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, uint64_t *dst_len,
                int *status, bool trailer, const PackPlanned *pl = nullptr);
 void check_message(zarc_gpu_t *h, size_t index);
@@ -1554,10 +1573,105 @@ int lines_deliver(const DecodedPart &p, const SearchReq &srch, SearchPart &sp)
     return ZARC_GPU_OK;
 }
 
+// what a part's ranges carry from one of their stages to the next
+struct RangePart {
+    int r0 = -1, r1 = -1;               // timer marks: in front of the count, behind the locate
+    float ms2 = 0;                      // the gather
+    std::vector<ZarcRangeFrame> frames; // what range_launch asked back (decoder order)
+};
+
+// ranges, first half: the frames are judged; count the line feeds of the frames that are asked for lines, work out T, a and b of every frame
+// and the byte offsets of both boundaries.  The descriptors are asked back here and are on the host behind the part's one wait.
+int range_launch(const DecodedPart &p, const RangeReq &rng, RangePart &rp)
+{
+    zarc_gpu *const h = p.h;
+    const size_t n = p.n;
+    int rc;
+    uint64_t slices = 0;
+    if ((rc = upload_slices(p, h->d_rg_slices, "read_ranges: batch too large", &slices))) return rc;
+    std::vector<ZarcRangeReq> req(n);
+    bool any_lines = false;
+    for (size_t i = 0; i < n; i++) {
+        const zarc_gpu_range &r = rng.range[p.order[i]];
+        req[i] = ZarcRangeReq{r.unit, r.flags, r.skip, r.take};
+        any_lines = any_lines || r.unit == ZARC_GPU_RANGE_LINES;
+    }
+    if ((rc = upload_bytes(h, h->d_rg_req, req.data(), n * sizeof(ZarcRangeReq)))) return rc;
+    ZHIP(h->d_rg_cnt.reserve(slices * 4));
+    ZHIP(h->d_rg_frames.reserve(n * sizeof(ZarcRangeFrame)));
+    ZHIP(h->d_rg_open.reserve(n * 8));
+    ZHIP(h->d_rg_nopen.reserve(8));
+    ZHIP(hipMemsetAsync(h->d_rg_nopen.p, 0, 8, h->stream));
+    const uint64_t *const d_slices = h->d_rg_slices.as<uint64_t>(), *const d_raw = h->d_raw_len.as<uint64_t>();
+    const ZarcRangeReq *const d_req = h->d_rg_req.as<ZarcRangeReq>();
+    ZarcRangeFrame *const d_frames = h->d_rg_frames.as<ZarcRangeFrame>();
+    ZHIP(p.t.mark(&rp.r0));
+    if (any_lines)
+        hipLaunchKernelGGL(zarc_range_count, dim3((unsigned)slices), dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, d_req,
+                           h->d_rg_cnt.as<uint32_t>());
+    hipLaunchKernelGGL(zarc_range_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, p.d_status, d_req,
+                       h->d_rg_cnt.as<uint32_t>(), d_frames, h->d_rg_open.as<uint32_t>(), h->d_rg_nopen.as<uint32_t>());
+    if (any_lines) // a fixed grid walks the list of open boundaries: its length is known on the device only
+        hipLaunchKernelGGL(zarc_range_locate, dim3((unsigned)std::min<size_t>(2 * n, (size_t)h->num_cus * 8)), dim3(256), 0, h->stream, h->d_rg_open.as<uint32_t>(),
+                           h->d_rg_nopen.as<uint32_t>(), d_slices, p.d_base, p.d_off, d_raw, d_frames);
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&rp.r1));
+    rp.frames.resize(n);
+    ZHIP(hipMemcpyAsync(rp.frames.data(), h->d_rg_frames.p, n * sizeof(ZarcRangeFrame), hipMemcpyDeviceToHost, h->stream));
+    return ZARC_GPU_OK;
+}
+
+// ranges, second half: res[] and the delivery rule in the caller's order, then the bytes this part delivers.  Waits once, for the text.
+int range_deliver(const DecodedPart &p, const RangeReq &rng, RangePart &rp)
+{
+    zarc_gpu *const h = p.h;
+    const size_t n = p.n;
+    RangeRun &run = *rng.run;
+    int rc;
+    std::vector<uint32_t> where(n); // the decoder's index of the caller's frame
+    for (size_t i = 0; i < n; i++) where[p.order[i]] = (uint32_t)i;
+    std::vector<ZarcRangeCopy> plan;
+    std::vector<uint64_t> blocks(1, 0);
+    uint64_t bytes = 0; // of this part
+    for (size_t c = 0; c < n; c++) {
+        const ZarcRangeFrame &F = rp.frames[where[c]];
+        zarc_gpu_range_result &r = rng.res[c];
+        memset(&r, 0, sizeof r);
+        if (!F.decoded) continue;
+        r.units = F.units; r.first = F.first; r.taken = F.taken; r.start = F.pos[0]; r.length = F.pos[1] - F.pos[0];
+        uint64_t e = r.length;
+        if (rng.max_bytes && e > rng.max_bytes) e = rng.max_bytes;
+        e = std::min<uint64_t>(e, rng.text_cap - run.text_used - bytes);
+        r.text_off = run.text_used + bytes; r.text_len = e;
+        if (!e) continue;
+        plan.push_back(ZarcRangeCopy{bytes, where[c], F.pos[0], (uint32_t)e, 0u});
+        blocks.push_back(blocks.back() + (e + ZARC_CHECK_SLICE - 1) / ZARC_CHECK_SLICE);
+        bytes += e;
+    }
+    if (!bytes) return ZARC_GPU_OK;
+    if (blocks.back() > 0x7FFFFFFFull) { set_error(h, "read_ranges: batch too large"); return ZARC_GPU_E_PARAM; }
+    if ((rc = upload_bytes(h, h->d_rg_plan, plan.data(), plan.size() * sizeof(ZarcRangeCopy)))) return rc;
+    if ((rc = upload_u64(h, h->d_rg_blocks, blocks.data(), blocks.size()))) return rc;
+    uint8_t *d_text = rng.d_text ? rng.d_text + run.text_used : nullptr;
+    if (!d_text) { ZHIP(h->d_rg_text.reserve(bytes + 16)); d_text = h->d_rg_text.as<uint8_t>(); } // (host form: sized by what the part delivers)
+    int r2, r3;
+    ZHIP(p.t.mark(&r2));
+    hipLaunchKernelGGL(zarc_range_gather, dim3((unsigned)blocks.back()), dim3(256), 0, h->stream, (uint32_t)plan.size(), h->d_rg_blocks.as<uint64_t>(),
+                       h->d_rg_plan.as<ZarcRangeCopy>(), p.d_base, p.d_off, d_text);
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&r3));
+    if (rng.h_text && (rc = lines_text_out(h, rng.h_text + run.text_used, d_text, bytes))) return rc;
+    ZHIP(hipStreamSynchronize(h->stream));
+    run.text_used += bytes;
+    rp.ms2 = elapsed(h, r2, r3);
+    return ZARC_GPU_OK;
+}
+
 // own_out: bytes of engine-owned output scratch this call decodes into (verify, read-back check); they count against the budget
 int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off_in, const uint64_t *frame_len_in,
                        void *d_dst_base, const uint64_t *dst_off_in, const uint64_t *raw_len_in, const uint8_t *expect_in, uint8_t *digest,
-                       int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr, DevBuf *order_out = nullptr, const SearchReq *srch = nullptr)
+                       int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr, DevBuf *order_out = nullptr, const SearchReq *srch = nullptr,
+                       const RangeReq *rng = nullptr)
 {
     int rc = 0;
     h->dec_scratch = 0;
@@ -1965,6 +2079,8 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     SearchPart sp;
     if (srch && (rc = search_launch(part, *srch, sp))) return rc;
     if (srch && srch->lines && (rc = lines_mark(part, *srch, sp))) return rc;
+    RangePart rp;
+    if (rng && (rc = range_launch(part, *rng, rp))) return rc;
     std::vector<int32_t> st_v;
     std::vector<uint8_t> dg_v;
     int32_t *st = (int32_t *)meta_take(h, n * 4); // results come back through the page-locked arena too, then go to the caller's order
@@ -1978,6 +2094,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     for (size_t i = 0; i < n; i++) { status[order[i]] = st[i]; memcpy(digest + (size_t)order[i] * 32, dg + i * 32, 32); }
     if (srch) search_scatter(part, *srch, sp);
     if (srch && srch->lines && (rc = lines_deliver(part, *srch, sp))) return rc;
+    if (rng && (rc = range_deliver(part, *rng, rp))) return rc;
     if (fastpath && diag_env("ZARC_GPU_DEC_STATS", 0)) { // diagnostics: how many frames had their sequences decoded ahead
         std::vector<uint32_t> fl(n);
         ZHIP(hipMemcpy(fl.data(), h->d_fast.p, n * 4, hipMemcpyDeviceToHost));
@@ -2012,6 +2129,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, e3);
     if (srch) { h->ms[ZARC_GPU_T_SEARCH] = elapsed(h, sp.e5, sp.e6); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, sp.e6); }
     if (srch && srch->lines) { h->ms[ZARC_GPU_T_LINES] = elapsed(h, sp.e6, sp.e7) + sp.lines_ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, sp.e7) + sp.lines_ms2; }
+    if (rng) { h->ms[ZARC_GPU_T_RANGE] = elapsed(h, rp.r0, rp.r1) + rp.ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, rp.r1) + rp.ms2; }
     return ZARC_GPU_OK;
 }
 
@@ -2023,7 +2141,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
 // that does not fit the device is halved after; a single frame runs alone whatever its size.
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                         void *d_dst_base, const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status,
-                        const PackCheck *chk = nullptr, const SearchReq *srch)
+                        const PackCheck *chk = nullptr, const SearchReq *srch, const RangeReq *rng)
 {
     const bool own = d_dst_base == nullptr;
     DevBuf &vout = h->vout_busy ? h->d_vout2 : h->d_vout; // (the read-back check inside a repack pass: d_vout holds what it compares with)
@@ -2042,7 +2160,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
     }
     if (attempt)
         rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, own ? vout.p : d_dst_base, own ? nullptr : dst_off, raw_len, expect, digest,
-                                status, own_bytes, chk, nullptr, srch);
+                                status, own_bytes, chk, nullptr, srch, rng);
     if ((rc != UNPACK_SPLIT && rc != ZARC_GPU_E_NOMEM) || n < 2) return rc == UNPACK_SPLIT ? ZARC_GPU_E_NOMEM : rc;
     (void)hipStreamSynchronize(h->stream);
     if (rc == ZARC_GPU_E_NOMEM) {
@@ -2062,8 +2180,9 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
         PackCheck sub{};
         if (chk) { sub = *chk; sub.first_bad += a; if (chk->entry_map) sub.entry_map += a; else sub.entry0 += (uint32_t)a; }
         const SearchReq ssub = srch ? part_of(*srch, a) : SearchReq{};
+        const RangeReq rsub = rng ? part_of(*rng, a) : RangeReq{};
         rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
-                                 digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr);
+                                 digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr, rng ? &rsub : nullptr);
         if (rc) return rc;
         for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] += h->ms[i];
     }
@@ -2331,8 +2450,41 @@ int search_call_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (la) { *la->rec_used = la->only_matches ? run.match_used : run.rec_used; *la->text_used = (size_t)run.text_used; }
     return rc;
 }
+
+// ---- read ranges (zarc_gpu_read_ranges_batch*): a verify pass that cuts a byte or line range out of what it decoded, per part ----
+// Every check of the call that is not verify's, and the call's request
+int range_prepare(zarc_gpu_t *h, size_t n, const zarc_gpu_range *range, uint64_t max_bytes, zarc_gpu_range_result *res, void *text, size_t text_cap,
+                  size_t *text_used, bool host_text, RangeRun *run, RangeReq *req)
+{
+    if (!range || !res || !text_used) { set_error(h, "read_ranges: range, res and text_used are needed"); return ZARC_GPU_E_PARAM; }
+    for (size_t i = 0; i < n; i++) {
+        if (range[i].unit != ZARC_GPU_RANGE_BYTES && range[i].unit != ZARC_GPU_RANGE_LINES) { set_error(h, "read_ranges: unknown unit"); return ZARC_GPU_E_PARAM; }
+        if (range[i].flags & ~(uint32_t)ZARC_GPU_RANGE_FROM_END) { set_error(h, "read_ranges: unknown flag"); return ZARC_GPU_E_PARAM; }
+    }
+    if (text_cap && !text) { set_error(h, "read_ranges: text_cap without a text buffer"); return ZARC_GPU_E_PARAM; }
+    *text_used = 0;
+    *req = RangeReq{range, res, max_bytes, text_cap, host_text ? nullptr : (uint8_t *)text, host_text ? (uint8_t *)text : nullptr, run};
+    return 0;
+}
 } // namespace
 extern "C" {
+
+int zarc_gpu_read_ranges_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                      const uint64_t *raw_len, const uint8_t *expect, const zarc_gpu_range *range, uint64_t max_bytes, uint8_t *digest,
+                                      int *status, zarc_gpu_range_result *res, void *d_text, size_t text_cap, size_t *text_used)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) { if (text_used) *text_used = 0; return ZARC_GPU_OK; }
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    RangeReq req;
+    RangeRun run;
+    if ((rc = range_prepare(h, n, range, max_bytes, res, d_text, text_cap, text_used, /*host_text=*/false, &run, &req))) return rc;
+    if ((rc = check_frame_sizes(h, n, frame_len, raw_len))) return rc;
+    rc = unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, nullptr, &req);
+    *text_used = (size_t)run.text_used;
+    return rc;
+}
 
 int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                                  const uint64_t *raw_len, const uint8_t *expect, const void *pattern, size_t pattern_len, unsigned flags,
@@ -2966,7 +3118,7 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 } // extern "C"
 namespace {
 int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
-                     const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const SearchReq *srch)
+                     const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const SearchReq *srch, const RangeReq *rng = nullptr)
 {
     int rc = 0;
     if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
@@ -3012,9 +3164,10 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
         // every chunk is a batch call of its own to the clocks and the descriptor arena; the copy counters are the whole call's (NestedCall).
         // The chunks are ranges of the caller's frames in the caller's order: the running remainder of rec_cap goes from one to the next
         const SearchReq sub = srch ? part_of(*srch, i0) : SearchReq{};
+        const RangeReq rsub = rng ? part_of(*rng, i0) : RangeReq{};
         if (!(rc = check_common(h, m)))
             rc = unpack_device_split(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, nullptr, nullptr, rlen.data() + i0,
-                                     expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0, nullptr, srch ? &sub : nullptr);
+                                     expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0, nullptr, srch ? &sub : nullptr, rng ? &rsub : nullptr);
         if (helper.joinable()) helper.join();
         if (rc) return rc;
         if (helper_rc) return helper_rc;
@@ -3049,6 +3202,22 @@ int zarc_gpu_verify_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
     if (rc) return rc;
     if (n == 0) return ZARC_GPU_OK;
     return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr);
+}
+// verify's chunk loop with the range kernels behind every chunk's verdict: the compressed bytes go up, the ranges' bytes come back
+int zarc_gpu_read_ranges_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                               const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const zarc_gpu_range *range, uint64_t max_bytes,
+                               uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, zarc_gpu_range_result *res, void *text, size_t text_cap, size_t *text_used)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) { if (text_used) *text_used = 0; return ZARC_GPU_OK; }
+    if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    RangeReq req;
+    RangeRun run;
+    if ((rc = range_prepare(h, n, range, max_bytes, res, text, text_cap, text_used, /*host_text=*/true, &run, &req))) return rc;
+    rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, &req);
+    *text_used = (size_t)run.text_used;
+    return rc;
 }
 int zarc_gpu_search_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                           const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *pattern, size_t pattern_len, unsigned flags,

@@ -322,6 +322,24 @@ __global__ void zarc_matches_emit_regex(uint64_t nrec, const ZarcLineRec *lrec, 
 // what 0 / 1: out[0 .. nrec] = exclusive sums (and the total) of the lines' bit words / of counts[]; 2: mrec[k].text_off, out[0] = the sum of text_len
 __global__ void zarc_matches_scan(uint32_t what, uint64_t nrec, const ZarcLineRec *lrec, const uint32_t *counts, ZarcMatchRec *mrec, uint64_t *out);
 __global__ void zarc_matches_gather(uint64_t nrec, const ZarcMatchRec *rec, const uint8_t *dec_base, const uint64_t *dec_off, uint8_t *text);
+// byte and line ranges of the decoded frames (zdec_ranges.hip); every per-frame array is in the decoder's order.  ZarcRangeReq is
+// zarc_gpu_range.  ZarcRangeFrame: what zarc_range_carry works out -- T, a, b - a, and per boundary (0: unit a, 1: unit b) either its
+// byte offset, or the slice of the part's grid that holds its 0x0A and which 0x0A of that slice it is (1-based); zarc_range_locate turns
+// the latter into offsets.  open[]: the boundaries (frame * 2 + which) that wait for it, *open_count of them (start: 0).
+// ZarcRangeCopy: `len` bytes from `start` of frame `frame` to text + dst; block_prefix counts the 64 KiB blocks of the copies in front.
+constexpr uint32_t ZARC_RANGE_BYTES = 0, ZARC_RANGE_LINES = 1, ZARC_RANGE_FROM_END = 1, ZARC_RANGE_NONE = 0xFFFFFFFFu;
+struct ZarcRangeReq { uint32_t unit, flags; uint64_t skip, take; };
+struct ZarcRangeFrame { uint32_t units, first, taken, pos[2], slice[2], ord[2], decoded; };
+struct ZarcRangeCopy { uint64_t dst; uint32_t frame, start, len, pad; };
+__global__ void zarc_range_count(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                 const int32_t *status, const ZarcRangeReq *req, uint32_t *cnt);
+__global__ void zarc_range_carry(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                                 const int32_t *status, const ZarcRangeReq *req, const uint32_t *cnt, ZarcRangeFrame *out, uint32_t *open,
+                                 uint32_t *open_count);
+__global__ void zarc_range_locate(const uint32_t *open, const uint32_t *open_count, const uint64_t *slice_prefix, const uint8_t *dec_base,
+                                  const uint64_t *dec_off, const uint64_t *raw_len, ZarcRangeFrame *out);
+__global__ void zarc_range_gather(uint32_t m, const uint64_t *block_prefix, const ZarcRangeCopy *plan, const uint8_t *dec_base, const uint64_t *dec_off,
+                                  uint8_t *text);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

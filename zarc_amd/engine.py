@@ -700,6 +700,71 @@ class Engine:
         include/zarc_gpu.h, zarc_gpu_regex_compile_ends).  Raises as search_matches() does.  Needs no device."""
         return regex_compile(self.lib, regex, icase, ends=True)
 
+    @staticmethod
+    def _ranges(ranges, n):
+        """-> the zarc_gpu_range array of `ranges`: one (unit, flags, skip, take) per frame"""
+        assert len(ranges) == n, "one range per frame"
+        arr = (_lib.Range * max(n, 1))()
+        for i, (unit, flags, skip, take) in enumerate(ranges):
+            arr[i].unit, arr[i].flags, arr[i].skip, arr[i].take = unit, flags, skip, take
+        return arr
+
+    @staticmethod
+    def _range_result(n, res):
+        return [(r.units, r.first, r.taken, r.start, r.length, r.text_off, r.text_len) for r in res[:n]]
+
+    def read_ranges(self, frames, raw_lens, ranges, expect=None, max_bytes=0, text_cap=1 << 20):
+        """verify() plus one byte or line range of every frame, cut out on the device -> (verdicts, res, text).  ranges[i] = (unit, flags,
+        skip, take) with unit RANGE_BYTES / RANGE_LINES, flags 0 / RANGE_FROM_END, take RANGE_ALL for "all the rest" (include/zarc_gpu.h has
+        the arithmetic).  verdicts = verify()'s list of (digest, status); res[i] = (units, first, taken, start, length, text_off,
+        text_len): the first five are the truth whatever the caps, the frame's delivered bytes are text[text_off:text_off + text_len] --
+        the first min(length, max_bytes or all, what text_cap leaves) of its range.  Only the compressed frames cross to the device and
+        only len(text) bytes come back."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        rng = self._ranges(ranges, n)
+        res = (_lib.RangeResult * max(n, 1))()
+        text = np.empty(max(text_cap, 1), dtype=np.uint8)
+        text_used = ctypes.c_size_t()
+        self._check(self.lib.zarc_gpu_read_ranges_batch(
+            self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None, rng, max_bytes,
+            dig.ctypes.data_as(ctypes.c_void_p), status, res, text.ctypes.data_as(ctypes.c_void_p), text_cap, ctypes.byref(text_used)))
+        return [(bytes(dig[i]), int(status[i])) for i in range(n)], self._range_result(n, res), bytes(text[:text_used.value])
+
+    def read_ranges_device(self, d_frames, frame_off, frame_len, raw_len, ranges, expect=None, max_bytes=0, text_cap=1 << 20):
+        """read_ranges() over frames resident on the device -> (verdicts, res, text).  The text is gathered into a device buffer of
+        text_cap bytes and copied back from there."""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        rng = self._ranges(ranges, n)
+        res = (_lib.RangeResult * max(n, 1))()
+        text_used = ctypes.c_size_t()
+        d_text = self.malloc(max(text_cap, 1))
+        try:
+            self._check(self.lib.zarc_gpu_read_ranges_batch_device(
+                self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None, rng, max_bytes,
+                dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), res, ctypes.c_void_p(d_text), text_cap,
+                ctypes.byref(text_used)))
+            text = bytes(self.d2h(d_text, text_used.value)) if text_used.value else b""
+        finally:
+            self.free(d_text)
+        return [(bytes(dig[i]), int(status[i])) for i in range(n)], self._range_result(n, res), text
+
     def repack(self, frames, raw_lens, expect=None):
         """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with
         the handle's current parameters -- the bytes pack() makes of what unpack() delivers -- and every other one gives None.  Only the

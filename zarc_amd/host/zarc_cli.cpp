@@ -182,7 +182,7 @@ bool safe_name(const std::vector<std::string> &name)
 
 int usage()
 {
-    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|grep|list-files> ...\n"
+    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|grep|cat|list-files> ...\n"
                          "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] [--split-blocks] [--check] PATH...\n"
                          "         --split-blocks  cut 64 KiB blocks where their statistics change (smaller frames on binaries / JSON; off by default)\n"
                          "         --check         decode every frame again on the device and compare it with its file before it is written; a mismatch\n"
@@ -231,6 +231,16 @@ int usage()
                          "         matches.  --batch-lines N bounds the lines that take part in one device call and the matches it brings back.  With -E the\n"
                          "         expression needs a second table of at most 64 states: one that -E accepts can be refused with it, before ARCHIVE is opened.\n"
                          "         It does not go with -v, -A, -B, -C or --tally\n"
+                         "       zarc cat [--filter REGEX]... [--verify DIGEST] [--gpus N] [--header] [--batch-bytes N]\n"
+                         "                [--head [-]N | --tail [+]N | --lines A:[B] | --head-bytes [-]N | --tail-bytes [+]N | --bytes A:[B]] ARCHIVE\n"
+                         "         writes the content of the regular files (grep's selection) to stdout, in directory order, as raw bytes.  At most one range\n"
+                         "         option: --head N / --tail N the first / last N lines, --head -N all but the last N, --tail +K from line K on, --lines A:B\n"
+                         "         lines A to B (1-based, inclusive; A: to the end), --bytes A:B bytes A to B (0-based, B excluded); the -bytes forms count\n"
+                         "         bytes.  N is plain decimal.  With a range option the range is cut out on the device, each distinct frame once, and only its\n"
+                         "         bytes come back; --batch-bytes N (default 268435456) is what one device call can bring back: what it cut off is fetched by a\n"
+                         "         further call, which decodes the frame again.  --header prints `==> PATH <==` in front of each file, as head -v.  A frame\n"
+                         "         that is not good prints nothing for its files and a message; a digest mismatch prints the content and a message.  Exit\n"
+                         "         status 0 iff every selected file was printed clean\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -758,6 +768,181 @@ int cmd_verify(const std::vector<std::string> &a)
     return failed ? 1 : 0;
 }
 
+// `zarc cat`: the content of the files that pass the filters, or one byte or line range of each, on stdout.  With a range option every
+// distinct content frame is decoded and judged on the device and only the range's bytes come back (zarc_gpu_read_ranges_batch); a frame
+// that many files share is read once and printed once per file.  Nothing is created, opened or changed in the file system.
+bool cat_number(const std::string &s, uint64_t *out) // plain decimal, no sign, no suffix
+{
+    if (s.empty() || s.size() > 20) return false;
+    unsigned __int128 v = 0;
+    for (char c : s) { if (c < '0' || c > '9') return false; v = v * 10 + (unsigned)(c - '0'); }
+    if (v > (unsigned __int128)UINT64_MAX) return false;
+    *out = (uint64_t)v;
+    return true;
+}
+// A:[B] -> a and, where given, b
+bool cat_pair(const std::string &s, uint64_t *a, uint64_t *b, bool *have_b)
+{
+    const size_t colon = s.find(':');
+    if (colon == std::string::npos || !cat_number(s.substr(0, colon), a)) return false;
+    *have_b = colon + 1 < s.size();
+    return !*have_b || cat_number(s.substr(colon + 1), b);
+}
+int cmd_cat(const std::vector<std::string> &a)
+{
+    std::string input, verify;
+    std::vector<std::regex> filters;
+    int gpus = 1, range_options = 0;
+    bool header = false;
+    uint64_t batch_bytes = (uint64_t)256 << 20;
+    zarc_gpu_range range{ZARC_GPU_RANGE_BYTES, 0, 0, ZARC_GPU_RANGE_ALL};
+    for (size_t i = 0; i < a.size(); i++) {
+        const bool value = i + 1 < a.size();
+        if (a[i] == "--filter" && value) filters.emplace_back(a[++i]);
+        else if (a[i] == "--verify" && value) verify = a[++i];
+        else if (a[i] == "--gpus" && value) gpus = std::atoi(a[++i].c_str());
+        else if (a[i] == "--header") header = true;
+        else if (a[i] == "--batch-bytes" && value) { if (!cat_number(a[++i], &batch_bytes) || batch_bytes < 1) return usage(); }
+        else if ((a[i] == "--head" || a[i] == "--head-bytes") && value) { // N: the first N; -N: all but the last N
+            const uint32_t unit = a[i] == "--head" ? ZARC_GPU_RANGE_LINES : ZARC_GPU_RANGE_BYTES;
+            const std::string v = a[++i];
+            uint64_t n;
+            const bool minus = !v.empty() && v[0] == '-';
+            if (!cat_number(minus ? v.substr(1) : v, &n)) return usage();
+            range = minus ? zarc_gpu_range{unit, ZARC_GPU_RANGE_FROM_END, n, ZARC_GPU_RANGE_ALL} : zarc_gpu_range{unit, 0, 0, n};
+            range_options++;
+        } else if ((a[i] == "--tail" || a[i] == "--tail-bytes") && value) { // N: the last N; +K: from the K-th on (+0 is +1, as tail has it)
+            const uint32_t unit = a[i] == "--tail" ? ZARC_GPU_RANGE_LINES : ZARC_GPU_RANGE_BYTES;
+            const std::string v = a[++i];
+            uint64_t n;
+            const bool plus = !v.empty() && v[0] == '+';
+            if (!cat_number(plus ? v.substr(1) : v, &n)) return usage();
+            range = plus ? zarc_gpu_range{unit, 0, n ? n - 1 : 0, ZARC_GPU_RANGE_ALL} : zarc_gpu_range{unit, ZARC_GPU_RANGE_FROM_END, 0, n};
+            range_options++;
+        } else if (a[i] == "--lines" && value) { // A:[B], 1-based, inclusive
+            uint64_t from, to = 0;
+            bool have_to;
+            if (!cat_pair(a[++i], &from, &to, &have_to) || from < 1 || (have_to && to < from)) return usage();
+            range = zarc_gpu_range{ZARC_GPU_RANGE_LINES, 0, from - 1, have_to ? to - from + 1 : ZARC_GPU_RANGE_ALL};
+            range_options++;
+        } else if (a[i] == "--bytes" && value) { // A:[B], 0-based, half-open
+            uint64_t from, to = 0;
+            bool have_to;
+            if (!cat_pair(a[++i], &from, &to, &have_to) || (have_to && to < from)) return usage();
+            range = zarc_gpu_range{ZARC_GPU_RANGE_BYTES, 0, from, have_to ? to - from : ZARC_GPU_RANGE_ALL};
+            range_options++;
+        } else if (!a[i].empty() && a[i][0] == '-') return usage();
+        else if (!input.empty()) return usage();
+        else input = a[i];
+    }
+    if (input.empty() || gpus < 1 || gpus > 64 || range_options > 1) return usage();
+    if (gpus > zarc_gpu_device_count()) { std::fprintf(stderr, "Error: --gpus %d but %d device(s) are usable\n", gpus, zarc_gpu_device_count()); return 1; }
+    Mapped m(input);
+    std::vector<int> devices;
+    for (int d = 0; d < gpus; d++) devices.push_back(d);
+    zarc::ArchiveReader rd(m.p, m.n, devices);
+    const std::string digest = base64(rd.trailer().digest.bytes.data(), 32);
+    if (!verify.empty()) {
+        if (verify != digest) { std::fprintf(stderr, "Error: integrity failure: zarc file digest is %s\n", digest.c_str()); return 1; }
+    } else std::fprintf(stderr, "digest: %s\n", digest.c_str());
+    unsigned long long n_files = 0, failed = 0, bytes = 0;
+    bool first_header = true;
+    // one file's turn: its header and bytes, or the message of a frame that is not good
+    auto print = [&](size_t file, const zarc::FrameReader::Result &r) {
+        const std::string path = to_path(rd.files()[file].name);
+        if (r.status != ZARC_GPU_FRAME_OK && r.status != ZARC_GPU_FRAME_DIGEST) {
+            std::fprintf(stderr, "ERROR %s path=%s\n", zarc_gpu_frame_status_name(r.status), path.c_str());
+            failed++;
+            return;
+        }
+        if (header) { std::fprintf(stdout, "%s==> %s <==\n", first_header ? "" : "\n", path.c_str()); first_header = false; } // head -v, byte for byte
+        if (!r.data.empty() && std::fwrite(r.data.data(), 1, r.data.size(), stdout) != r.data.size()) throw zarc::Error(ZARC_GPU_E_PARAM, "stdout: write failed");
+        bytes += r.data.size();
+        if (!r.verify.value_or(false)) { std::fprintf(stderr, "ERROR frame verification failed! path=%s\n", path.c_str()); failed++; } // delivered all the same (unpack.rs:118-120)
+    };
+    // the selection is grep's: regular files that pass the filters, in directory order
+    std::vector<size_t> selected;
+    std::map<zarc::Digest, size_t> uses; // files of every distinct frame that are still to print
+    for (size_t i = 0; i < rd.files().size(); i++) {
+        const zarc::File &f = rd.files()[i];
+        if (!f.is_normal() || !passes(filters, to_path(f.name))) continue;
+        n_files++;
+        if (!rd.frames().count(*f.digest)) { std::fprintf(stderr, "WARN frame not found path=%s\n", to_path(f.name).c_str()); failed++; continue; }
+        selected.push_back(i);
+        uses[*f.digest]++;
+    }
+    const size_t n_frames = uses.size();
+    const size_t BATCH = (size_t)1 << 30;
+    if (!range_options) { // whole files: unpack's path
+        std::vector<size_t> batch;
+        size_t weight = 0;
+        auto flush = [&]() {
+            if (batch.empty()) return;
+            const std::vector<zarc::FrameReader::Result> res = rd.read_files(batch);
+            for (size_t k = 0; k < batch.size(); k++) print(batch[k], res[k]);
+            batch.clear();
+            weight = 0;
+        };
+        for (size_t i : selected) {
+            batch.push_back(i);
+            weight += (size_t)rd.frames().at(*rd.files()[i].digest).uncompressed;
+            if (weight >= BATCH) flush();
+        }
+        flush();
+    } else {
+        // batches of distinct frames in the order their first file comes up; a batch's files are printed in directory order behind it, and
+        // a frame's result stays until its last file is out
+        std::map<zarc::Digest, zarc::FrameReader::Result> have;
+        std::vector<zarc::Digest> batch;
+        std::vector<size_t> waiting; // files of this batch's turn
+        size_t weight = 0;
+        auto flush = [&]() {
+            if (!batch.empty()) {
+                std::vector<zarc::FrameReader::Result> res = rd.read_ranges(batch, std::vector<zarc_gpu_range>(batch.size(), range), 0, (size_t)batch_bytes);
+                for (;;) { // what --batch-bytes cut off: the rest by BYTES ranges (the frames are decoded again), until nothing is cut
+                    std::vector<size_t> cut;
+                    std::vector<zarc::Digest> again;
+                    std::vector<zarc_gpu_range> rest;
+                    for (size_t k = 0; k < batch.size(); k++)
+                        if (res[k].data.size() < res[k].range.length) {
+                            cut.push_back(k); again.push_back(batch[k]);
+                            rest.push_back(zarc_gpu_range{ZARC_GPU_RANGE_BYTES, 0, res[k].range.start + res[k].data.size(), res[k].range.length - res[k].data.size()});
+                        }
+                    if (cut.empty()) break;
+                    const std::vector<zarc::FrameReader::Result> more = rd.read_ranges(again, rest, 0, (size_t)batch_bytes);
+                    for (size_t j = 0; j < cut.size(); j++) res[cut[j]].data.insert(res[cut[j]].data.end(), more[j].data.begin(), more[j].data.end());
+                    LOGF(3, "read_ranges", "continued frames=%zu", cut.size());
+                }
+                for (size_t k = 0; k < batch.size(); k++) have.emplace(batch[k], std::move(res[k]));
+                LOGF(3, "read_ranges", "frames=%zu bytes=%zu", batch.size(), weight);
+            }
+            for (size_t i : waiting) {
+                const zarc::Digest &d = *rd.files()[i].digest;
+                print(i, have.at(d));
+                if (--uses[d] == 0) have.erase(d);
+            }
+            batch.clear();
+            waiting.clear();
+            weight = 0;
+        };
+        std::map<zarc::Digest, bool> asked;
+        for (size_t i : selected) {
+            const zarc::Digest &d = *rd.files()[i].digest;
+            waiting.push_back(i);
+            if (!asked[d]) {
+                asked[d] = true;
+                batch.push_back(d);
+                weight += (size_t)rd.frames().at(d).uncompressed;
+                if (weight >= BATCH) flush();
+            }
+        }
+        flush();
+    }
+    std::fflush(stdout);
+    std::fprintf(stderr, "printed %llu files (%zu frames, %llu bytes), %llu failed\n", n_files, n_frames, bytes, failed);
+    return failed ? 1 : 0;
+}
+
 // `zarc grep`: which files contain this byte string?  Every distinct content frame behind the files that pass the filters is decoded,
 // judged and searched on the device (zarc_gpu_search_batch; with -e / -f / --tally a set of strings in one pass, zarc_gpu_search_set_batch;
 // with -E a regular expression, zarc_gpu_search_regex_batch):
@@ -1230,7 +1415,7 @@ int main(int argc, char **argv)
         else if (a == "--log-file") {
             have_log_file = true;
             // num_args = 0..=1: a following word that is not a subcommand is the path
-            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0 || std::string("grep").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
+            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0 || std::string("grep").rfind(n, 0) == 0 || std::string("cat").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
         } else break;
     }
     if (i >= argc) return usage();
@@ -1245,6 +1430,7 @@ int main(int argc, char **argv)
         if (!verb.empty() && std::string("verify").rfind(verb, 0) == 0) return cmd_verify(rest);
         if (!verb.empty() && std::string("repack").rfind(verb, 0) == 0) return cmd_repack(rest);
         if (!verb.empty() && std::string("grep").rfind(verb, 0) == 0) return cmd_grep(rest);
+        if (!verb.empty() && std::string("cat").rfind(verb, 0) == 0) return cmd_cat(rest);
         return usage();
     } catch (const zarc::Error &e) {
         std::fprintf(stderr, "Error: %s\n", e.what());

@@ -18,6 +18,7 @@
 #include "zarc_host.hpp"
 #include <algorithm>
 #include <ctime>
+#include <tuple>
 
 namespace zarc {
 
@@ -522,6 +523,30 @@ class ArchiveReader {
             wanted.push_back(it->second);
         }
         return reader_.matches_content_frames(data_, len_, wanted, what, icase, max_lines, max_line, line_cap, rec_cap, hits);
+    }
+    // check_frames plus one byte or line range of every frame, cut out on the device (FrameReader::range_content_frames): per digest, in
+    // order, `range` and in `data` the bytes the delivery rule gives it.  ranges[i] belongs to digests[i].  Each distinct (digest, range)
+    // pair is read once: a later copy of a pair gets the first one's result and counts nothing against text_cap.
+    std::vector<FrameReader::Result> read_ranges(const std::vector<Digest> &digests, const std::vector<zarc_gpu_range> &ranges, uint64_t max_bytes = 0,
+                                                 size_t text_cap = (size_t)256 << 20)
+    {
+        if (ranges.size() != digests.size()) throw Error(ZARC_GPU_E_PARAM, "one range per digest");
+        using Key = std::tuple<Digest, uint32_t, uint32_t, uint64_t, uint64_t>;
+        std::map<Key, size_t> seen;
+        std::vector<size_t> slot(digests.size());
+        std::vector<Frame> wanted;
+        std::vector<zarc_gpu_range> rg;
+        for (size_t i = 0; i < digests.size(); i++) {
+            auto it = frames_.find(digests[i]);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            const auto ins = seen.emplace(Key{digests[i], ranges[i].unit, ranges[i].flags, ranges[i].skip, ranges[i].take}, wanted.size());
+            if (ins.second) { wanted.push_back(it->second); rg.push_back(ranges[i]); }
+            slot[i] = ins.first->second;
+        }
+        const std::vector<FrameReader::Result> got = reader_.range_content_frames(data_, len_, wanted, rg, max_bytes, text_cap);
+        std::vector<FrameReader::Result> out;
+        for (size_t i = 0; i < digests.size(); i++) out.push_back(got[slot[i]]);
+        return out;
     }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()

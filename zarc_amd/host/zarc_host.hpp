@@ -399,6 +399,9 @@ class FrameReader {
         struct Match { uint64_t start, length, number, line_start, which; std::vector<uint8_t> text; };
         uint64_t matches = 0;
         std::vector<Match> match_records;
+        // range_content_frames: zarc_gpu_range_result's first five fields -- the truth whatever the caps; the delivered bytes are `data`
+        struct Range { uint64_t units = 0, first = 0, taken = 0, start = 0, length = 0; };
+        Range range;
     };
     explicit FrameReader(int device = 0) : FrameReader(std::vector<int>{device}) {}
     explicit FrameReader(const std::vector<int> &devices)
@@ -563,6 +566,76 @@ class FrameReader {
         for (Result &r : out) { // the record rule over the merged list (a handle saw fewer frames in front of this one: it delivered no less)
             if (r.match_records.size() > left) r.match_records.resize(left);
             left -= r.match_records.size();
+        }
+        return out;
+    }
+
+    // check_content_frames plus one byte or line range of every frame, cut out on the device (zarc_gpu_read_ranges_batch): per frame
+    // {digest, verify, status}, `range` and in `data` the bytes the delivery rule gives it -- frames in the caller's order, frame i the first
+    // min(length, max_bytes or all, what text_cap leaves) bytes of its range.  ranges[i] belongs to wanted[i]; the same frame may stand in
+    // the batch several times.  Every handle runs its share with the caller's caps, the shares are merged in the caller's order and the
+    // rule is applied once more on the merged list (a handle saw fewer frames in front of a frame: it delivered no less): the results are
+    // identical for every number of handles.  Only the delivered bytes come back.
+    std::vector<Result> range_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const std::vector<zarc_gpu_range> &ranges,
+                                             uint64_t max_bytes = 0, size_t text_cap = (size_t)256 << 20)
+    {
+        const size_t n = wanted.size();
+        if (ranges.size() != n) throw Error(ZARC_GPU_E_PARAM, "one range per frame");
+        for (const zarc_gpu_range &r : ranges) {
+            if (r.unit != ZARC_GPU_RANGE_BYTES && r.unit != ZARC_GPU_RANGE_LINES) throw Error(ZARC_GPU_E_PARAM, "unknown range unit");
+            if (r.flags & ~(uint32_t)ZARC_GPU_RANGE_FROM_END) throw Error(ZARC_GPU_E_PARAM, "unknown range flag");
+        }
+        std::vector<Result> out(n);
+        check_frame_records(archive_len, wanted);
+        if (n == 0) return out;
+        std::vector<size_t> rl(n);
+        for (size_t i = 0; i < n; i++) rl[i] = wanted[i].uncompressed;
+        const size_t g = engines_.size();
+        const auto share = shard_assign(rl.data(), n, g);
+        std::vector<int> rc(g, ZARC_GPU_OK);
+        auto range_share = [&](size_t d) {
+            const std::vector<size_t> &idx = share[d];
+            const size_t m = idx.size();
+            if (m == 0) return;
+            std::vector<const void *> fp(m);
+            std::vector<size_t> fl(m), ul(m);
+            std::vector<Digest> expect(m), got(m);
+            std::vector<int> status(m);
+            std::vector<zarc_gpu_range> rg(m);
+            std::vector<zarc_gpu_range_result> res(m);
+            uint64_t room = 0; // no frame delivers more than its content, or than max_bytes
+            for (size_t j = 0; j < m; j++) {
+                const Frame &f = wanted[idx[j]];
+                fp[j] = archive + f.offset; fl[j] = f.length; ul[j] = f.uncompressed; expect[j] = f.digest; rg[j] = ranges[idx[j]];
+                room += max_bytes ? std::min<uint64_t>(f.uncompressed, max_bytes) : f.uncompressed;
+            }
+            const size_t cap = (size_t)std::min<uint64_t>(text_cap, room);
+            std::unique_ptr<uint8_t, void (*)(void *)> text((uint8_t *)std::malloc(std::max<size_t>(1, cap)), std::free);
+            if (!text) { rc[d] = ZARC_GPU_E_NOMEM; return; }
+            size_t text_used = 0;
+            rc[d] = zarc_gpu_read_ranges_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), rg.data(), max_bytes,
+                                               (uint8_t(*)[32])got.data(), status.data(), res.data(), text.get(), cap, &text_used);
+            if (rc[d] != ZARC_GPU_OK) return;
+            for (size_t j = 0; j < m; j++) {
+                Result &r = out[idx[j]];
+                r.status = status[j];
+                r.digest = got[j];
+                if (status[j] == ZARC_GPU_FRAME_OK || status[j] == ZARC_GPU_FRAME_DIGEST) r.verify = got[j] == expect[j];
+                r.range = Result::Range{res[j].units, res[j].first, res[j].taken, res[j].start, res[j].length};
+                r.data.assign(text.get() + res[j].text_off, text.get() + res[j].text_off + res[j].text_len);
+            }
+        };
+        if (g == 1) range_share(0);
+        else {
+            std::vector<std::thread> th;
+            for (size_t d = 0; d < g; d++) th.emplace_back(range_share, d);
+            for (auto &t : th) t.join();
+        }
+        for (size_t d = 0; d < g; d++) engines_[d]->check(rc[d]);
+        uint64_t left = text_cap;
+        for (Result &r : out) { // the delivery rule over the merged list
+            if (r.data.size() > left) r.data.resize((size_t)left);
+            left -= r.data.size();
         }
         return out;
     }
