@@ -49,7 +49,8 @@ extern "C" {
                                   zarc_gpu_search_set_*, and zarc_gpu_regex_compile with zarc_gpu_search_regex_* (new symbols; ZARC_GPU_T_COUNT stays 12), then
                                   zarc_gpu_select_lines_batch* (new symbols and types; nothing existing changes), then zarc_gpu_search_matches_batch* with
                                   zarc_gpu_regex_compile_ends and zarc_gpu_match (the same: new symbols and one new type), then
-                                  zarc_gpu_read_ranges_batch* with ZARC_GPU_T_RANGE (new symbols and types; ZARC_GPU_T_COUNT grew from 12 to 13) */
+                                  zarc_gpu_read_ranges_batch* with ZARC_GPU_T_RANGE (new symbols and types; ZARC_GPU_T_COUNT grew from 12 to 13), then
+                                  zarc_gpu_count_batch* with zarc_gpu_wc and ZARC_GPU_T_WC (the same; ZARC_GPU_T_COUNT grew from 13 to 14) */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -650,6 +651,39 @@ int zarc_gpu_read_ranges_batch_device(zarc_gpu_t *h, size_t n, const void *d_fra
                                       uint64_t max_bytes, uint8_t *digest /* n*32 */, int *status, zarc_gpu_range_result *res /* HOST, n */,
                                       void *d_text /* DEVICE pointer */, size_t text_cap, size_t *text_used);
 
+/* ---- count: lines, words, characters and the longest line of frames, counted on the device -------------------------------------------------- */
+/* What `tar -xO file | wc` answers, for a batch of frames: every frame is decoded and judged as zarc_gpu_verify_batch does it, its content
+ * is read once more where the decoded bytes lie, and 64 bytes of counts per frame come back.  Arguments, status[i], digest[i] and error
+ * returns are EXACTLY those of zarc_gpu_verify_batch* for the same frames and `expect`; res (HOST memory in every form, n records) is the
+ * one addition, and a missing res is ZARC_GPU_E_PARAM behind verify's own checks.  n == 0: ZARC_GPU_OK.  A frame or raw length of 4 GiB or
+ * more: ZARC_GPU_E_UNSUPPORTED.
+ * A frame takes part when it decoded: ZARC_GPU_FRAME_OK, and ZARC_GPU_FRAME_DIGEST as well (the decoded set of the ranges call).  With
+ * content d of raw_len[i] bytes:
+ *   - lines: the number of 0x0A bytes, as `wc -l` counts.
+ *   - words: the number of positions p with !sp(d[p]) && (p == 0 || sp(d[p - 1])), where sp(c) holds for 0x09 .. 0x0D and 0x20: the
+ *     maximal runs of other bytes.  It is what `wc -w` gives in the C locale on printable text.
+ *   - chars: the number of bytes with (c & 0xC0) != 0x80 -- bytes that are no UTF-8 continuation byte.  For valid UTF-8 it is the number of
+ *     code points (`wc -m` under a UTF-8 locale); for any other bytes it is still this definition.
+ *   - max_line: the length in BYTES of the longest piece of d split at 0x0A; the unterminated piece behind the last 0x0A counts, the 0x0A
+ *     itself does not.  It is NOT GNU `wc -L`, which is a display width that expands tabs and skips non-printable bytes.
+ *   - max_line_start: the offset of the first byte of the LOWEST such piece; max_line_no: that piece's 1-based line number -- the 0x0A bytes
+ *     in front of it, plus 1 -- the number zarc_gpu_search_lines_batch reports and a ZARC_GPU_RANGE_LINES range with skip = max_line_no - 1
+ *     names.
+ *   - Empty content: all fields 0.  Every other status: all fields 0.  reserved = 0.
+ *   - res is identical for every ZARC_GPU_PX_SCRATCH_MB, every ZARC_GPU_PX_STAGE_CHUNK, both forms and every number of handles a caller
+ *     deals the batch to.
+ *   - zarc_gpu_last_copy_bytes: H2D = sum of frame_len in the host form, 0 in the device form; D2H = 0 (the 64 bytes a frame are descriptors,
+ *     not content, as in verify).
+ *   - zarc_gpu_last_kernel_ms: verify's timers, ZARC_GPU_T_WC for zarc_wc_* summed over the parts of the call, ZARC_GPU_T_TOTAL including it.
+ *   - Cost: decode and both hash passes are verify's and run in full; beside them the decoded bytes are read once. */
+typedef struct { uint64_t lines, words, chars, max_line, max_line_start, max_line_no, reserved[2]; } zarc_gpu_wc;   /* 64 bytes */
+int zarc_gpu_count_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                         const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status,
+                         zarc_gpu_wc *res /* n */);
+int zarc_gpu_count_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, uint8_t *digest /* n*32 */, int *status,
+                                zarc_gpu_wc *res /* HOST, n */);
+
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,
                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN]);
@@ -677,7 +711,8 @@ enum {
     ZARC_GPU_T_SEARCH = 10,   /* search: zarc_search_scan (a set: zarc_set_scan and zarc_set_which; a regex: zarc_regex_summary, _carry and _scan), summed over the parts of a call; < 0 or 0 after any other call */
     ZARC_GPU_T_LINES = 11,    /* search_lines: zarc_lines_* (mark, carry, emit, scan, gather; a set or a regex: its twins of mark and emit; select_lines: zarc_lines_select_* in place of mark, carry and emit; search_matches: zarc_matches_* behind emit, in place of scan and gather), summed over the parts of a call; < 0 or 0 after any other call */
     ZARC_GPU_T_RANGE = 12,    /* read_ranges: zarc_range_* (count, carry, locate, gather), summed over the parts of a call; < 0 or 0 after any other call */
-    ZARC_GPU_T_COUNT = 13
+    ZARC_GPU_T_WC = 13,       /* count: zarc_wc_* (count, carry), summed over the parts of a call; < 0 or 0 after any other call */
+    ZARC_GPU_T_COUNT = 14
 };
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which);
 /* Content bytes the most recent batch call moved between host and device (descriptor arrays, statuses, digests not counted).  Every

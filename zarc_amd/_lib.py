@@ -48,6 +48,8 @@ REGEX_MAX_PATTERN, REGEX_MAX_STATES = 1024, 64  # zarc_gpu_search_regex_*: the l
 T_RANGE = 12   # zarc_range_* of a read_ranges call (summed over its parts)
 # zarc_gpu_read_ranges_batch*: zarc_gpu_range.unit, .flags, and the take that means "all the rest"
 RANGE_BYTES, RANGE_LINES, RANGE_FROM_END, RANGE_ALL = 0, 1, 1, 2 ** 64 - 1
+T_WC = 13      # zarc_wc_* of a count call (summed over its parts)
+T_COUNT = 14   # the number of timers
 
 EXPORTS = [
     "zarc_gpu_abi_version", "zarc_gpu_level_finder", "zarc_gpu_parameter_advisory", "zarc_gpu_device_count", "zarc_gpu_create", "zarc_gpu_destroy", "zarc_gpu_set_parameter", "zarc_gpu_get_params",
@@ -59,7 +61,7 @@ EXPORTS = [
     "zarc_gpu_regex_compile", "zarc_gpu_search_regex_batch", "zarc_gpu_search_regex_batch_device", "zarc_gpu_search_regex_lines_batch",
     "zarc_gpu_search_regex_lines_batch_device", "zarc_gpu_select_lines_batch", "zarc_gpu_select_lines_batch_device",
     "zarc_gpu_regex_compile_ends", "zarc_gpu_search_matches_batch", "zarc_gpu_search_matches_batch_device",
-    "zarc_gpu_read_ranges_batch", "zarc_gpu_read_ranges_batch_device",
+    "zarc_gpu_read_ranges_batch", "zarc_gpu_read_ranges_batch_device", "zarc_gpu_count_batch", "zarc_gpu_count_batch_device",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -136,6 +138,11 @@ class Range(ctypes.Structure):
 class RangeResult(ctypes.Structure):
     """zarc_gpu_range_result: what a read_ranges call found and delivered of one frame"""
     _fields_ = [(n, ctypes.c_uint64) for n in ("units", "first", "taken", "start", "length", "text_off", "text_len", "reserved")]
+
+
+class Wc(ctypes.Structure):
+    """zarc_gpu_wc: what a count call found of one frame"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("lines", "words", "chars", "max_line", "max_line_start", "max_line_no")] + [("reserved", ctypes.c_uint64 * 2)]
 
 
 class RegexDfa(ctypes.Structure):
@@ -223,6 +230,9 @@ def load(path=None):
     rp, rrp = c.POINTER(Range), c.POINTER(RangeResult)
     lib.zarc_gpu_read_ranges_batch.argtypes = [vp, sz, vpp, szp, szp, vp, rp, c.c_uint64, vp, ip, rrp, vp, sz, szp]
     lib.zarc_gpu_read_ranges_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, rp, c.c_uint64, vp, ip, rrp, vp, sz, szp]
+    wp = c.POINTER(Wc)
+    lib.zarc_gpu_count_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vp, ip, wp]
+    lib.zarc_gpu_count_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, ip, wp]
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

@@ -137,6 +137,8 @@ struct zarc_gpu {
     DevBuf d_rg_slices, d_rg_req, d_rg_cnt;     // slice prefix; the ranges (decoder order); 0x0A bytes of every slice of a LINES frame
     DevBuf d_rg_frames, d_rg_open, d_rg_nopen;  // ZarcRangeFrame of every frame (decoder order); the boundaries that wait for zarc_range_locate, and how many
     DevBuf d_rg_plan, d_rg_blocks, d_rg_text;   // what the host decided: the part's copies and their block prefix; (host form) the part's text
+    // line, word, character and longest-line counts (zarc_gpu_count_batch*): zarc_wc_* over d_vout behind the verdict of a verify pass, per part
+    DevBuf d_wc_slices, d_wc_rec, d_wc_out;     // slice prefix; ZarcWcSlice of every slice of the part's grid; ZarcWcFrame of every frame (decoder order)
     bool vout_busy = false;     // a repack pass is between its halves: d_vout is not the check's to take
     uint64_t dec_scratch = 0;   // decoder scratch (sequences, literals, tables) of the most recent decode, as counted against the budget
     // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
@@ -715,14 +717,21 @@ struct RangeReq {
     RangeRun *run;
 };
 RangeReq part_of(RangeReq r, size_t a) { r.range += a; r.res += a; return r; }
+// A verify pass that counts what it decoded (zarc_gpu_count_batch*): zarc_wc_* run behind the verdict, per part, while that part's bytes
+// are in d_vout.  Every frame's answer is its own, so the parts of a call share nothing.
+struct WcReq { zarc_gpu_wc *res; }; // host, in the caller's order, this part's first frame first
+WcReq part_of(WcReq r, size_t a) { r.res += a; return r; }
+// what the count kernels keep in the handle's scratch for a part of n frames and `raw` decoded bytes (counted against the budget)
+uint64_t wc_scratch(size_t n, uint64_t raw) { return (raw / ZARC_CHECK_SLICE + n) * sizeof(ZarcWcSlice) + n * sizeof(ZarcWcFrame); }
 int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
+static_assert(sizeof(ZarcWcFrame) == sizeof(zarc_gpu_wc) && sizeof(zarc_gpu_wc) == 64, "the device's record is the caller's");
 static_assert(sizeof(ZarcRangeReq) == sizeof(zarc_gpu_range), "the device's range is the caller's");
 static_assert(sizeof(ZarcLineRec) == sizeof(zarc_gpu_line), "the device's record is the caller's");
 static_assert(sizeof(ZarcMatchRec) == sizeof(zarc_gpu_match), "the device's record is the caller's");
 
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, void *d_dst_base,
                         const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk,
-                        const SearchReq *srch = nullptr, const RangeReq *rng = nullptr);
+                        const SearchReq *srch = nullptr, const RangeReq *rng = nullptr, const WcReq *wc = nullptr);
 int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, uint64_t *dst_len,
                int *status, bool trailer, const PackPlanned *pl = nullptr);
 void check_message(zarc_gpu_t *h, size_t index);
@@ -1667,11 +1676,47 @@ int range_deliver(const DecodedPart &p, const RangeReq &rng, RangePart &rp)
     return ZARC_GPU_OK;
 }
 
+// what a part's counts carry from their launch to their delivery
+struct WcPart {
+    int w0 = -1, w1 = -1;           // timer marks: in front of the count, behind the carry
+    std::vector<ZarcWcFrame> out;   // what wc_launch asked back (decoder order)
+};
+
+// counts, first half: the frames are judged; one record per slice, then one zarc_gpu_wc per frame.  The answers are asked back here and are
+// on the host behind the part's one wait.
+int wc_launch(const DecodedPart &p, WcPart &wp)
+{
+    zarc_gpu *const h = p.h;
+    const size_t n = p.n;
+    int rc;
+    uint64_t slices = 0;
+    if ((rc = upload_slices(p, h->d_wc_slices, "count: batch too large", &slices))) return rc;
+    ZHIP(h->d_wc_rec.reserve(slices * sizeof(ZarcWcSlice)));
+    ZHIP(h->d_wc_out.reserve(n * sizeof(ZarcWcFrame)));
+    const uint64_t *const d_slices = h->d_wc_slices.as<uint64_t>(), *const d_raw = h->d_raw_len.as<uint64_t>();
+    ZHIP(p.t.mark(&wp.w0));
+    hipLaunchKernelGGL(zarc_wc_count, dim3((unsigned)slices), dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, p.d_status,
+                       h->d_wc_rec.as<ZarcWcSlice>());
+    hipLaunchKernelGGL(zarc_wc_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (uint32_t)n, d_slices, d_raw, p.d_status,
+                       h->d_wc_rec.as<ZarcWcSlice>(), h->d_wc_out.as<ZarcWcFrame>());
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&wp.w1));
+    wp.out.resize(n);
+    ZHIP(hipMemcpyAsync(wp.out.data(), h->d_wc_out.p, n * sizeof(ZarcWcFrame), hipMemcpyDeviceToHost, h->stream));
+    return ZARC_GPU_OK;
+}
+
+// counts, second half: to the caller's order
+void wc_deliver(const DecodedPart &p, const WcReq &wc, const WcPart &wp)
+{
+    for (size_t i = 0; i < p.n; i++) memcpy(&wc.res[p.order[i]], &wp.out[i], sizeof(zarc_gpu_wc));
+}
+
 // own_out: bytes of engine-owned output scratch this call decodes into (verify, read-back check); they count against the budget
 int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off_in, const uint64_t *frame_len_in,
                        void *d_dst_base, const uint64_t *dst_off_in, const uint64_t *raw_len_in, const uint8_t *expect_in, uint8_t *digest,
                        int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr, DevBuf *order_out = nullptr, const SearchReq *srch = nullptr,
-                       const RangeReq *rng = nullptr)
+                       const RangeReq *rng = nullptr, const WcReq *wc = nullptr)
 {
     int rc = 0;
     h->dec_scratch = 0;
@@ -1840,6 +1885,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
             total_seqs = total; total_lits = lit_total;
         }
         h->dec_scratch = total_seqs * 8 + total_lits + nslots * (uint64_t)(ZDEC_TABLE_CELLS * 2 + sizeof(ZdecBlock) + 32);
+        if (wc) h->dec_scratch += wc_scratch(n, total_raw); // the slices' records lie in the handle's scratch beside the decoder's
         if (h->scratch_budget && n > 1 && own_out + h->dec_scratch > h->scratch_budget) return UNPACK_SPLIT;
         if (!lean) {
             if ((rc = upload_u64(h, h->d_seqidx, seqidx.data(), nslots))) return rc;
@@ -2081,6 +2127,8 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (srch && srch->lines && (rc = lines_mark(part, *srch, sp))) return rc;
     RangePart rp;
     if (rng && (rc = range_launch(part, *rng, rp))) return rc;
+    WcPart wp;
+    if (wc && (rc = wc_launch(part, wp))) return rc;
     std::vector<int32_t> st_v;
     std::vector<uint8_t> dg_v;
     int32_t *st = (int32_t *)meta_take(h, n * 4); // results come back through the page-locked arena too, then go to the caller's order
@@ -2095,6 +2143,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (srch) search_scatter(part, *srch, sp);
     if (srch && srch->lines && (rc = lines_deliver(part, *srch, sp))) return rc;
     if (rng && (rc = range_deliver(part, *rng, rp))) return rc;
+    if (wc) wc_deliver(part, *wc, wp);
     if (fastpath && diag_env("ZARC_GPU_DEC_STATS", 0)) { // diagnostics: how many frames had their sequences decoded ahead
         std::vector<uint32_t> fl(n);
         ZHIP(hipMemcpy(fl.data(), h->d_fast.p, n * 4, hipMemcpyDeviceToHost));
@@ -2130,6 +2179,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (srch) { h->ms[ZARC_GPU_T_SEARCH] = elapsed(h, sp.e5, sp.e6); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, sp.e6); }
     if (srch && srch->lines) { h->ms[ZARC_GPU_T_LINES] = elapsed(h, sp.e6, sp.e7) + sp.lines_ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, sp.e7) + sp.lines_ms2; }
     if (rng) { h->ms[ZARC_GPU_T_RANGE] = elapsed(h, rp.r0, rp.r1) + rp.ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, rp.r1) + rp.ms2; }
+    if (wc) { h->ms[ZARC_GPU_T_WC] = elapsed(h, wp.w0, wp.w1); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, wp.w1); }
     return ZARC_GPU_OK;
 }
 
@@ -2141,7 +2191,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
 // that does not fit the device is halved after; a single frame runs alone whatever its size.
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                         void *d_dst_base, const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status,
-                        const PackCheck *chk = nullptr, const SearchReq *srch, const RangeReq *rng)
+                        const PackCheck *chk = nullptr, const SearchReq *srch, const RangeReq *rng, const WcReq *wc)
 {
     const bool own = d_dst_base == nullptr;
     DevBuf &vout = h->vout_busy ? h->d_vout2 : h->d_vout; // (the read-back check inside a repack pass: d_vout holds what it compares with)
@@ -2160,7 +2210,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
     }
     if (attempt)
         rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, own ? vout.p : d_dst_base, own ? nullptr : dst_off, raw_len, expect, digest,
-                                status, own_bytes, chk, nullptr, srch, rng);
+                                status, own_bytes, chk, nullptr, srch, rng, wc);
     if ((rc != UNPACK_SPLIT && rc != ZARC_GPU_E_NOMEM) || n < 2) return rc == UNPACK_SPLIT ? ZARC_GPU_E_NOMEM : rc;
     (void)hipStreamSynchronize(h->stream);
     if (rc == ZARC_GPU_E_NOMEM) {
@@ -2181,8 +2231,10 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
         if (chk) { sub = *chk; sub.first_bad += a; if (chk->entry_map) sub.entry_map += a; else sub.entry0 += (uint32_t)a; }
         const SearchReq ssub = srch ? part_of(*srch, a) : SearchReq{};
         const RangeReq rsub = rng ? part_of(*rng, a) : RangeReq{};
+        const WcReq wsub = wc ? part_of(*wc, a) : WcReq{};
         rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
-                                 digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr, rng ? &rsub : nullptr);
+                                 digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr, rng ? &rsub : nullptr,
+                                 wc ? &wsub : nullptr);
         if (rc) return rc;
         for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] += h->ms[i];
     }
@@ -2484,6 +2536,19 @@ int zarc_gpu_read_ranges_batch_device(zarc_gpu_t *h, size_t n, const void *d_fra
     rc = unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, nullptr, &req);
     *text_used = (size_t)run.text_used;
     return rc;
+}
+
+// verify_batch_device with the count kernels behind every part's verdict
+int zarc_gpu_count_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, zarc_gpu_wc *res)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    if (!res) { set_error(h, "count: res is needed"); return ZARC_GPU_E_PARAM; }
+    const WcReq req{res};
+    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, nullptr, nullptr, &req);
 }
 
 int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
@@ -3118,7 +3183,8 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 } // extern "C"
 namespace {
 int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
-                     const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const SearchReq *srch, const RangeReq *rng = nullptr)
+                     const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const SearchReq *srch, const RangeReq *rng = nullptr,
+                     const WcReq *wc = nullptr)
 {
     int rc = 0;
     if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
@@ -3165,9 +3231,11 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
         // The chunks are ranges of the caller's frames in the caller's order: the running remainder of rec_cap goes from one to the next
         const SearchReq sub = srch ? part_of(*srch, i0) : SearchReq{};
         const RangeReq rsub = rng ? part_of(*rng, i0) : RangeReq{};
+        const WcReq wsub = wc ? part_of(*wc, i0) : WcReq{};
         if (!(rc = check_common(h, m)))
             rc = unpack_device_split(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, nullptr, nullptr, rlen.data() + i0,
-                                     expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0, nullptr, srch ? &sub : nullptr, rng ? &rsub : nullptr);
+                                     expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0, nullptr, srch ? &sub : nullptr, rng ? &rsub : nullptr,
+                                     wc ? &wsub : nullptr);
         if (helper.joinable()) helper.join();
         if (rc) return rc;
         if (helper_rc) return helper_rc;
@@ -3218,6 +3286,18 @@ int zarc_gpu_read_ranges_batch(zarc_gpu_t *h, size_t n, const void *const *frame
     rc = verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, &req);
     *text_used = (size_t)run.text_used;
     return rc;
+}
+// verify's chunk loop with the count kernels behind every chunk's verdict: the compressed bytes go up, 64 bytes a frame come back
+int zarc_gpu_count_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                         const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, zarc_gpu_wc *res)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    if (!res) { set_error(h, "count: res is needed"); return ZARC_GPU_E_PARAM; }
+    const WcReq req{res};
+    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, nullptr, &req);
 }
 int zarc_gpu_search_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                           const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *pattern, size_t pattern_len, unsigned flags,

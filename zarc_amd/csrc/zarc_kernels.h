@@ -340,6 +340,18 @@ __global__ void zarc_range_locate(const uint32_t *open, const uint32_t *open_cou
                                   const uint64_t *dec_off, const uint64_t *raw_len, ZarcRangeFrame *out);
 __global__ void zarc_range_gather(uint32_t m, const uint64_t *block_prefix, const ZarcRangeCopy *plan, const uint8_t *dec_base, const uint64_t *dec_off,
                                   uint8_t *text);
+// line, word, character and longest-line counts of the decoded frames (zdec_wc.hip); every per-frame array is in the decoder's order.
+// ZarcWcSlice: what zarc_wc_count knows of one slice of the part's grid -- its 0x0A bytes, word starts and bytes that are no UTF-8
+// continuation byte; its first and last 0x0A (absolute offsets in the frame; ZARC_WC_NONE: none); the longest line between two 0x0A
+// bytes of the slice (best_len ZARC_WC_NONE: none), where it starts and how many 0x0A bytes of the slice lie in front of it.
+// ZarcWcFrame is zarc_gpu_wc.
+constexpr uint32_t ZARC_WC_NONE = 0xFFFFFFFFu;
+struct ZarcWcSlice { uint32_t nls, words, chars, first, last, best_len, best_start, best_ord; };
+struct ZarcWcFrame { uint64_t lines, words, chars, max_line, max_line_start, max_line_no, reserved[2]; };
+__global__ void zarc_wc_count(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                              const int32_t *status, ZarcWcSlice *rec);
+__global__ void zarc_wc_carry(uint32_t n, const uint64_t *slice_prefix, const uint64_t *raw_len, const int32_t *status, const ZarcWcSlice *rec,
+                              ZarcWcFrame *out);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

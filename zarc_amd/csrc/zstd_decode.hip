@@ -2189,3 +2189,4 @@ __global__ void __launch_bounds__(64) zarc_zdec_literals(const uint8_t *__restri
 #include "zdec_select.hip" // zarc_lines_select_*: the lines a search selects (inverted, with context), behind every matcher's bitmaps
 #include "zdec_matches.hip" // zarc_matches_*: every match of the delivered lines, cut out where it starts and ends
 #include "zdec_ranges.hip" // zarc_range_*: byte and line ranges of the decoded frames, cut out where they lie
+#include "zdec_wc.hip" // zarc_wc_*: line, word, character and longest-line counts of the decoded frames

@@ -765,6 +765,49 @@ class Engine:
             self.free(d_text)
         return [(bytes(dig[i]), int(status[i])) for i in range(n)], self._range_result(n, res), text
 
+    @staticmethod
+    def _wc_result(n, res):
+        return [(r.lines, r.words, r.chars, r.max_line, r.max_line_start, r.max_line_no) for r in res[:n]]
+
+    def count(self, frames, raw_lens, expect=None):
+        """verify() plus what `wc` says of every frame, counted on the device -> (verdicts, counts).  verdicts = verify()'s list of
+        (digest, status); counts[i] = (lines, words, chars, max_line, max_line_start, max_line_no): 0x0A bytes, runs of bytes that are
+        not white space, bytes that are no UTF-8 continuation byte, the byte length of the longest line, where the lowest such line
+        starts and its 1-based number (include/zarc_gpu.h has the definitions).  A frame that did not decode gives zeros.  Only the
+        compressed frames cross to the device and 64 bytes a frame come back."""
+        n = len(frames)
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        res = (_lib.Wc * max(n, 1))()
+        self._check(self.lib.zarc_gpu_count_batch(
+            self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            dig.ctypes.data_as(ctypes.c_void_p), status, res))
+        return [(bytes(dig[i]), int(status[i])) for i in range(n)], self._wc_result(n, res)
+
+    def count_device(self, d_frames, frame_off, frame_len, raw_len, expect=None):
+        """count() over frames resident on the device -> (verdicts, counts)"""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        res = (_lib.Wc * max(n, 1))()
+        self._check(self.lib.zarc_gpu_count_batch_device(
+            self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), res))
+        return [(bytes(dig[i]), int(status[i])) for i in range(n)], self._wc_result(n, res)
+
     def repack(self, frames, raw_lens, expect=None):
         """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with
         the handle's current parameters -- the bytes pack() makes of what unpack() delivers -- and every other one gives None.  Only the

@@ -182,7 +182,7 @@ bool safe_name(const std::vector<std::string> &name)
 
 int usage()
 {
-    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|grep|cat|list-files> ...\n"
+    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|grep|cat|wc|list-files> ...\n"
                          "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] [--split-blocks] [--check] PATH...\n"
                          "         --split-blocks  cut 64 KiB blocks where their statistics change (smaller frames on binaries / JSON; off by default)\n"
                          "         --check         decode every frame again on the device and compare it with its file before it is written; a mismatch\n"
@@ -241,6 +241,15 @@ int usage()
                          "         further call, which decodes the frame again.  --header prints `==> PATH <==` in front of each file, as head -v.  A frame\n"
                          "         that is not good prints nothing for its files and a message; a digest mismatch prints the content and a message.  Exit\n"
                          "         status 0 iff every selected file was printed clean\n"
+                         "       zarc wc [-l] [-w] [-m] [-c] [--max-line-bytes] [--longest] [--filter REGEX]... [--verify DIGEST] [--gpus N] ARCHIVE\n"
+                         "         counts the content of the regular files (grep's selection) on the device, each distinct frame once: one line per file, in\n"
+                         "         directory order, with the selected counts in the fixed order lines (-l), words (-w), characters (-m), bytes (-c),\n"
+                         "         max-line-bytes, each followed by one space, then the path.  There is no column padding.  Without a count option: lines,\n"
+                         "         words and bytes, as wc.  A word is a run of bytes other than space, tab, LF, VT, FF and CR; a character is a byte that is no\n"
+                         "         UTF-8 continuation byte; --max-line-bytes is the longest line in BYTES (not wc -L's display width).  --longest implies it\n"
+                         "         and prints that column as LEN:LINE_NO:OFFSET of the first such line -- the line `zarc cat --lines LINE_NO:LINE_NO` cuts out.\n"
+                         "         More than one file: a last line `... total` with the sums and the largest max-line-bytes.  A frame that is not good prints\n"
+                         "         a message and no line.  Exit status 0 iff every selected file was counted clean\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -943,6 +952,124 @@ int cmd_cat(const std::vector<std::string> &a)
     return failed ? 1 : 0;
 }
 
+// `zarc wc`: lines, words, characters, bytes and the longest line of the files that pass the filters.  Every distinct content frame is
+// decoded, judged and counted on the device (zarc_gpu_count_batch) and 64 bytes a frame come back; a frame that many files share is counted
+// once and reported for each of them.  Nothing is created, opened or changed in the file system.
+int cmd_wc(const std::vector<std::string> &a)
+{
+    std::string input, verify;
+    std::vector<std::regex> filters;
+    int gpus = 1;
+    bool want_l = false, want_w = false, want_m = false, want_c = false, want_max = false, longest = false;
+    for (size_t i = 0; i < a.size(); i++) {
+        const bool value = i + 1 < a.size();
+        if (a[i] == "--filter" && value) filters.emplace_back(a[++i]);
+        else if (a[i] == "--verify" && value) verify = a[++i];
+        else if (a[i] == "--gpus" && value) gpus = std::atoi(a[++i].c_str());
+        else if (a[i] == "-l") want_l = true;
+        else if (a[i] == "-w") want_w = true;
+        else if (a[i] == "-m") want_m = true;
+        else if (a[i] == "-c") want_c = true;
+        else if (a[i] == "--max-line-bytes") want_max = true;
+        else if (a[i] == "--longest") longest = want_max = true;
+        else if (!a[i].empty() && a[i][0] == '-') return usage();
+        else if (!input.empty()) return usage();
+        else input = a[i];
+    }
+    if (input.empty() || gpus < 1 || gpus > 64) return usage();
+    if (!(want_l || want_w || want_m || want_c || want_max)) want_l = want_w = want_c = true; // as wc
+    if (gpus > zarc_gpu_device_count()) { std::fprintf(stderr, "Error: --gpus %d but %d device(s) are usable\n", gpus, zarc_gpu_device_count()); return 1; }
+    Mapped m(input);
+    std::vector<int> devices;
+    for (int d = 0; d < gpus; d++) devices.push_back(d);
+    zarc::ArchiveReader rd(m.p, m.n, devices);
+    const std::string digest = base64(rd.trailer().digest.bytes.data(), 32);
+    if (!verify.empty()) {
+        if (verify != digest) { std::fprintf(stderr, "Error: integrity failure: zarc file digest is %s\n", digest.c_str()); return 1; }
+    } else std::fprintf(stderr, "digest: %s\n", digest.c_str());
+    unsigned long long n_files = 0, failed = 0, printed = 0;
+    zarc::FrameReader::Result::Count total;
+    uint64_t total_bytes = 0;
+    auto row = [&](const zarc::FrameReader::Result::Count &c, uint64_t bytes, bool is_total, const std::string &name) {
+        std::string s;
+        if (want_l) s += std::to_string(c.lines) + " ";
+        if (want_w) s += std::to_string(c.words) + " ";
+        if (want_m) s += std::to_string(c.chars) + " ";
+        if (want_c) s += std::to_string(bytes) + " ";
+        if (want_max) {
+            s += std::to_string(c.max_line);
+            if (longest && !is_total) s += ":" + std::to_string(c.max_line_no) + ":" + std::to_string(c.max_line_start);
+            s += " ";
+        }
+        std::fprintf(stdout, "%s%s\n", s.c_str(), name.c_str());
+    };
+    // one file's turn: its line, or the message of a frame that is not good
+    auto print = [&](size_t file, const zarc::FrameReader::Result &r) {
+        const std::string path = to_path(rd.files()[file].name);
+        const bool decoded = r.status == ZARC_GPU_FRAME_OK || r.status == ZARC_GPU_FRAME_DIGEST;
+        if (!decoded || !r.verify.value_or(false)) { // verify's messages
+            if (decoded) std::fprintf(stderr, "ERROR frame verification failed! path=%s\n", path.c_str());
+            else std::fprintf(stderr, "ERROR %s path=%s\n", zarc_gpu_frame_status_name(r.status), path.c_str());
+            failed++;
+            return;
+        }
+        const uint64_t bytes = rd.frames().at(*rd.files()[file].digest).uncompressed;
+        row(r.wc, bytes, false, path);
+        printed++;
+        total.lines += r.wc.lines; total.words += r.wc.words; total.chars += r.wc.chars; total_bytes += bytes;
+        total.max_line = std::max(total.max_line, r.wc.max_line);
+    };
+    // the selection is grep's: regular files that pass the filters, in directory order.  Batches of distinct frames in the order their first
+    // file comes up; a batch's files are printed in directory order behind it, and a frame's result stays until its last file is out
+    std::vector<size_t> selected;
+    std::map<zarc::Digest, size_t> uses;
+    for (size_t i = 0; i < rd.files().size(); i++) {
+        const zarc::File &f = rd.files()[i];
+        if (!f.is_normal() || !passes(filters, to_path(f.name))) continue;
+        n_files++;
+        if (!rd.frames().count(*f.digest)) { std::fprintf(stderr, "WARN frame not found path=%s\n", to_path(f.name).c_str()); failed++; continue; }
+        selected.push_back(i);
+        uses[*f.digest]++;
+    }
+    const size_t n_frames = uses.size();
+    const size_t BATCH = (size_t)1 << 30;
+    std::map<zarc::Digest, zarc::FrameReader::Result> have;
+    std::vector<zarc::Digest> batch;
+    std::vector<size_t> waiting; // files of this batch's turn
+    size_t weight = 0;
+    auto flush = [&]() {
+        if (!batch.empty()) {
+            std::vector<zarc::FrameReader::Result> res = rd.count_frames(batch);
+            for (size_t k = 0; k < batch.size(); k++) have.emplace(batch[k], std::move(res[k]));
+            LOGF(3, "count_frames", "frames=%zu bytes=%zu", batch.size(), weight);
+        }
+        for (size_t i : waiting) {
+            const zarc::Digest &d = *rd.files()[i].digest;
+            print(i, have.at(d));
+            if (--uses[d] == 0) have.erase(d);
+        }
+        batch.clear();
+        waiting.clear();
+        weight = 0;
+    };
+    std::map<zarc::Digest, bool> asked;
+    for (size_t i : selected) {
+        const zarc::Digest &d = *rd.files()[i].digest;
+        waiting.push_back(i);
+        if (!asked[d]) {
+            asked[d] = true;
+            batch.push_back(d);
+            weight += (size_t)rd.frames().at(d).uncompressed;
+            if (weight >= BATCH) flush();
+        }
+    }
+    flush();
+    if (printed > 1) row(total, total_bytes, true, "total");
+    std::fflush(stdout);
+    std::fprintf(stderr, "counted %llu files (%zu frames), %llu failed\n", n_files, n_frames, failed);
+    return failed ? 1 : 0;
+}
+
 // `zarc grep`: which files contain this byte string?  Every distinct content frame behind the files that pass the filters is decoded,
 // judged and searched on the device (zarc_gpu_search_batch; with -e / -f / --tally a set of strings in one pass, zarc_gpu_search_set_batch;
 // with -E a regular expression, zarc_gpu_search_regex_batch):
@@ -1415,7 +1542,7 @@ int main(int argc, char **argv)
         else if (a == "--log-file") {
             have_log_file = true;
             // num_args = 0..=1: a following word that is not a subcommand is the path
-            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0 || std::string("grep").rfind(n, 0) == 0 || std::string("cat").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
+            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0 || std::string("grep").rfind(n, 0) == 0 || std::string("cat").rfind(n, 0) == 0 || std::string("wc").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
         } else break;
     }
     if (i >= argc) return usage();
@@ -1431,6 +1558,7 @@ int main(int argc, char **argv)
         if (!verb.empty() && std::string("repack").rfind(verb, 0) == 0) return cmd_repack(rest);
         if (!verb.empty() && std::string("grep").rfind(verb, 0) == 0) return cmd_grep(rest);
         if (!verb.empty() && std::string("cat").rfind(verb, 0) == 0) return cmd_cat(rest);
+        if (!verb.empty() && std::string("wc").rfind(verb, 0) == 0) return cmd_wc(rest);
         return usage();
     } catch (const zarc::Error &e) {
         std::fprintf(stderr, "Error: %s\n", e.what());

@@ -548,6 +548,25 @@ class ArchiveReader {
         for (size_t i = 0; i < digests.size(); i++) out.push_back(got[slot[i]]);
         return out;
     }
+    // check_frames plus what `wc` says of every frame, counted on the device (FrameReader::count_content_frames): per digest, in order,
+    // `wc`.  Each distinct digest is counted once: a later copy gets the first one's result.
+    std::vector<FrameReader::Result> count_frames(const std::vector<Digest> &digests)
+    {
+        std::map<Digest, size_t> seen;
+        std::vector<size_t> slot(digests.size());
+        std::vector<Frame> wanted;
+        for (size_t i = 0; i < digests.size(); i++) {
+            auto it = frames_.find(digests[i]);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            const auto ins = seen.emplace(digests[i], wanted.size());
+            if (ins.second) wanted.push_back(it->second);
+            slot[i] = ins.first->second;
+        }
+        const std::vector<FrameReader::Result> got = reader_.count_content_frames(data_, len_, wanted);
+        std::vector<FrameReader::Result> out;
+        for (size_t i = 0; i < digests.size(); i++) out.push_back(got[slot[i]]);
+        return out;
+    }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()
     {

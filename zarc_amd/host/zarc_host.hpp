@@ -402,6 +402,9 @@ class FrameReader {
         // range_content_frames: zarc_gpu_range_result's first five fields -- the truth whatever the caps; the delivered bytes are `data`
         struct Range { uint64_t units = 0, first = 0, taken = 0, start = 0, length = 0; };
         Range range;
+        // count_content_frames: zarc_gpu_wc's six fields; all zero for a frame that did not decode
+        struct Count { uint64_t lines = 0, words = 0, chars = 0, max_line = 0, max_line_start = 0, max_line_no = 0; };
+        Count wc;
     };
     explicit FrameReader(int device = 0) : FrameReader(std::vector<int>{device}) {}
     explicit FrameReader(const std::vector<int> &devices)
@@ -637,6 +640,54 @@ class FrameReader {
             if (r.data.size() > left) r.data.resize((size_t)left);
             left -= r.data.size();
         }
+        return out;
+    }
+
+    // check_content_frames plus what `wc` says of every frame, counted on the device (zarc_gpu_count_batch): per frame {digest, verify,
+    // status} and `wc`.  The same dealing over the handles, one thread per handle; every frame's answer is its own, so the results are in
+    // the caller's order and identical for every number of handles.  Only 64 bytes a frame come back.
+    std::vector<Result> count_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted)
+    {
+        const size_t n = wanted.size();
+        std::vector<Result> out(n);
+        check_frame_records(archive_len, wanted);
+        if (n == 0) return out;
+        std::vector<size_t> rl(n);
+        for (size_t i = 0; i < n; i++) rl[i] = wanted[i].uncompressed;
+        const size_t g = engines_.size();
+        const auto share = shard_assign(rl.data(), n, g);
+        std::vector<int> rc(g, ZARC_GPU_OK);
+        auto count_share = [&](size_t d) {
+            const std::vector<size_t> &idx = share[d];
+            const size_t m = idx.size();
+            if (m == 0) return;
+            std::vector<const void *> fp(m);
+            std::vector<size_t> fl(m), ul(m);
+            std::vector<Digest> expect(m), got(m);
+            std::vector<int> status(m);
+            std::vector<zarc_gpu_wc> res(m);
+            for (size_t j = 0; j < m; j++) {
+                const Frame &f = wanted[idx[j]];
+                fp[j] = archive + f.offset; fl[j] = f.length; ul[j] = f.uncompressed; expect[j] = f.digest;
+            }
+            rc[d] = zarc_gpu_count_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), (uint8_t(*)[32])got.data(),
+                                         status.data(), res.data());
+            if (rc[d] != ZARC_GPU_OK) return;
+            for (size_t j = 0; j < m; j++) {
+                Result &r = out[idx[j]];
+                r.status = status[j];
+                r.digest = got[j];
+                if (status[j] == ZARC_GPU_FRAME_OK || status[j] == ZARC_GPU_FRAME_DIGEST) r.verify = got[j] == expect[j];
+                r.wc = Result::Count{res[j].lines, res[j].words, res[j].chars, res[j].max_line, res[j].max_line_start, res[j].max_line_no};
+            }
+        };
+        if (g == 1) count_share(0);
+        else {
+            std::vector<std::thread> th;
+            for (size_t d = 0; d < g; d++) th.emplace_back(count_share, d);
+            for (auto &t : th) t.join();
+        }
+        for (size_t d = 0; d < g; d++) engines_[d]->check(rc[d]);
         return out;
     }
 
