@@ -50,7 +50,8 @@ extern "C" {
                                   zarc_gpu_select_lines_batch* (new symbols and types; nothing existing changes), then zarc_gpu_search_matches_batch* with
                                   zarc_gpu_regex_compile_ends and zarc_gpu_match (the same: new symbols and one new type), then
                                   zarc_gpu_read_ranges_batch* with ZARC_GPU_T_RANGE (new symbols and types; ZARC_GPU_T_COUNT grew from 12 to 13), then
-                                  zarc_gpu_count_batch* with zarc_gpu_wc and ZARC_GPU_T_WC (the same; ZARC_GPU_T_COUNT grew from 13 to 14) */
+                                  zarc_gpu_count_batch* with zarc_gpu_wc and ZARC_GPU_T_WC (the same; ZARC_GPU_T_COUNT grew from 13 to 14), then
+                                  zarc_gpu_compare_batch* with zarc_gpu_cmp and zarc_gpu_last_compare_ms (new symbols and one new type; ZARC_GPU_T_COUNT stays 14) */
 #define ZARC_GPU_DIGEST_LEN 32  /* DigestType::digest_len(), crates/zarc/src/integrity.rs:100-104 */
 #define ZARC_GPU_ALIGN 16       /* device-resident entries / outputs must start 16-byte aligned   */
 #define ZARC_GPU_PAD 64         /* readable slack required after the last byte of a device arena   */
@@ -683,6 +684,49 @@ int zarc_gpu_count_batch(zarc_gpu_t *h, size_t n, const void *const *frame, cons
 int zarc_gpu_count_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                                 const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, uint8_t *digest /* n*32 */, int *status,
                                 zarc_gpu_wc *res /* HOST, n */);
+
+/* ---- compare: frames against other bytes, compared on the device ---------------------------------------------------------------------------- */
+/* What `tar --compare` and `cmp` answer, for a batch of pairs: every frame is decoded and judged as zarc_gpu_verify_batch does it, its content
+ * is read once more where the decoded bytes lie, next to the other side's bytes, and 64 bytes per pair come back.  Arguments, status[i],
+ * digest[i] and error returns are EXACTLY those of zarc_gpu_verify_batch* for the same frames and `expect`; other, other_len and res (HOST
+ * memory in every form, n records) are the additions.  A missing res, other or other_len is ZARC_GPU_E_PARAM behind verify's own checks;
+ * other[i] may be NULL only where other_len[i] == 0.  n == 0: ZARC_GPU_OK.  A frame, raw or other length of 4 GiB or more:
+ * ZARC_GPU_E_UNSUPPORTED.  Device form: other i lies at d_other_base + other_off[i], other_off[i] a multiple of ZARC_GPU_ALIGN (else
+ * ZARC_GPU_E_PARAM), with ZARC_GPU_PAD readable bytes behind the arena -- pack's rules for device-resident sources.
+ * A frame takes part when it decoded: ZARC_GPU_FRAME_OK, and ZARC_GPU_FRAME_DIGEST as well.  With A the content of raw_len[i] bytes, B the
+ * other[i] of other_len[i] bytes and common = min(|A|, |B|):
+ *   - differing: the number of p < common with A[p] != B[p] -- what `cmp -l` lists.
+ *   - prefix: the lowest such p; common where there is none.
+ *   - relation: ZARC_GPU_CMP_DIFFER when differing > 0; otherwise EQUAL, FRAME_IS_PREFIX or OTHER_IS_PREFIX by the lengths.
+ *   - line: 1 + the number of 0x0A in A[0 .. prefix) -- the line `cmp` prints.  No exception: for EQUAL it is lines + 1.
+ *   - byte_a, byte_b: A[prefix] and B[prefix]; ZARC_GPU_CMP_EOF where that side ends at prefix.
+ *   - suffix: the largest s <= common - prefix with A[|A| - s ..] == B[|B| - s ..]: the common tail, which never overlaps the common head.
+ *     With |A| == |B| it is the distance from the last differing byte to the end.
+ *   - Both sides empty: EQUAL, all counts 0, line 1.  A frame that did not decode: every field 0 (ZARC_GPU_CMP_NONE).  reserved = 0.
+ *   - res is identical for every ZARC_GPU_PX_SCRATCH_MB, every ZARC_GPU_PX_STAGE_CHUNK, both forms and every number of handles a caller
+ *     deals the batch to.  In the host form the staged other bytes count against the budget and the chunk weight with the frames: chunks
+ *     are cut over max(in, out, other).
+ *   - zarc_gpu_last_copy_bytes: H2D = sum of frame_len + sum of other_len in the host form, 0 in the device form; D2H = 0.
+ *   - zarc_gpu_last_compare_ms: zarc_cmp_* summed over the parts of the call; <= 0 after any other call.  ZARC_GPU_T_TOTAL includes it.
+ *     (The timer enum is not extended: ZARC_GPU_T_COUNT stays 14.)
+ *   - Cost: decode and both hash passes are verify's and run in full; beside them both sides are read once, and where the lengths differ
+ *     the common part of the other side a second time, shifted. */
+enum { ZARC_GPU_CMP_NONE = 0,             /* the frame did not decode: every field 0 */
+       ZARC_GPU_CMP_EQUAL = 1,            /* same length, same bytes */
+       ZARC_GPU_CMP_DIFFER = 2,           /* a byte below min(raw_len, other_len) differs */
+       ZARC_GPU_CMP_FRAME_IS_PREFIX = 3,  /* the content is a proper prefix of `other` (cmp: EOF on the archive's side) */
+       ZARC_GPU_CMP_OTHER_IS_PREFIX = 4 };/* `other` is a proper prefix of the content */
+#define ZARC_GPU_CMP_EOF 256u             /* byte_a / byte_b where that side has no byte at `prefix` */
+typedef struct { uint32_t relation, byte_a, byte_b, reserved0;
+                 uint64_t prefix, line, differing, suffix, reserved[2]; } zarc_gpu_cmp;   /* 64 bytes */
+int zarc_gpu_compare_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                           const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN] /* or NULL */, const void *const *other, const size_t *other_len,
+                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, zarc_gpu_cmp *res /* n */);
+int zarc_gpu_compare_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                  const uint64_t *raw_len, const uint8_t *expect /* n*32 or NULL */, const void *d_other_base,
+                                  const uint64_t *other_off, const uint64_t *other_len, uint8_t *digest /* n*32 */, int *status,
+                                  zarc_gpu_cmp *res /* HOST, n */);
+float zarc_gpu_last_compare_ms(const zarc_gpu_t *h);
 
 /* ---- digest only (DigestType::verify_data, integrity.rs:107-117) ------------------------------- */
 int zarc_gpu_blake3_batch(zarc_gpu_t *h, size_t n, const void *const *src, const size_t *len,

@@ -50,6 +50,9 @@ T_RANGE = 12   # zarc_range_* of a read_ranges call (summed over its parts)
 RANGE_BYTES, RANGE_LINES, RANGE_FROM_END, RANGE_ALL = 0, 1, 1, 2 ** 64 - 1
 T_WC = 13      # zarc_wc_* of a count call (summed over its parts)
 T_COUNT = 14   # the number of timers
+# zarc_gpu_compare_batch*: zarc_gpu_cmp.relation, and byte_a / byte_b where that side has no byte at `prefix`
+CMP_NONE, CMP_EQUAL, CMP_DIFFER, CMP_FRAME_IS_PREFIX, CMP_OTHER_IS_PREFIX = 0, 1, 2, 3, 4
+CMP_EOF = 256
 
 EXPORTS = [
     "zarc_gpu_abi_version", "zarc_gpu_level_finder", "zarc_gpu_parameter_advisory", "zarc_gpu_device_count", "zarc_gpu_create", "zarc_gpu_destroy", "zarc_gpu_set_parameter", "zarc_gpu_get_params",
@@ -62,6 +65,7 @@ EXPORTS = [
     "zarc_gpu_search_regex_lines_batch_device", "zarc_gpu_select_lines_batch", "zarc_gpu_select_lines_batch_device",
     "zarc_gpu_regex_compile_ends", "zarc_gpu_search_matches_batch", "zarc_gpu_search_matches_batch_device",
     "zarc_gpu_read_ranges_batch", "zarc_gpu_read_ranges_batch_device", "zarc_gpu_count_batch", "zarc_gpu_count_batch_device",
+    "zarc_gpu_compare_batch", "zarc_gpu_compare_batch_device", "zarc_gpu_last_compare_ms",
     "zarc_gpu_blake3_batch", "zarc_gpu_blake3_batch_device", "zarc_gpu_xxh64_batch_device", "zarc_gpu_last_kernel_ms",
     "zarc_gpu_corpus_fill_device", "zarc_gpu_device_malloc", "zarc_gpu_device_free", "zarc_gpu_memcpy_h2d", "zarc_gpu_memcpy_d2h",
 ]
@@ -143,6 +147,12 @@ class RangeResult(ctypes.Structure):
 class Wc(ctypes.Structure):
     """zarc_gpu_wc: what a count call found of one frame"""
     _fields_ = [(n, ctypes.c_uint64) for n in ("lines", "words", "chars", "max_line", "max_line_start", "max_line_no")] + [("reserved", ctypes.c_uint64 * 2)]
+
+
+class Cmp(ctypes.Structure):
+    """zarc_gpu_cmp: what a compare call found of one pair"""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("relation", "byte_a", "byte_b", "reserved0")] + \
+               [(n, ctypes.c_uint64) for n in ("prefix", "line", "differing", "suffix")] + [("reserved", ctypes.c_uint64 * 2)]
 
 
 class RegexDfa(ctypes.Structure):
@@ -233,6 +243,11 @@ def load(path=None):
     wp = c.POINTER(Wc)
     lib.zarc_gpu_count_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vp, ip, wp]
     lib.zarc_gpu_count_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, ip, wp]
+    cp = c.POINTER(Cmp)
+    lib.zarc_gpu_compare_batch.argtypes = [vp, sz, vpp, szp, szp, vp, vpp, szp, vp, ip, cp]
+    lib.zarc_gpu_compare_batch_device.argtypes = [vp, sz, vp, u64p, u64p, u64p, vp, vp, u64p, u64p, vp, ip, cp]
+    lib.zarc_gpu_last_compare_ms.argtypes = [vp]
+    lib.zarc_gpu_last_compare_ms.restype = c.c_float
     lib.zarc_gpu_last_copy_bytes.argtypes = [vp, c.c_int]
     lib.zarc_gpu_last_copy_bytes.restype = c.c_uint64
     lib.zarc_gpu_blake3_batch.argtypes = [vp, sz, vpp, szp, vp]

@@ -139,6 +139,10 @@ struct zarc_gpu {
     DevBuf d_rg_plan, d_rg_blocks, d_rg_text;   // what the host decided: the part's copies and their block prefix; (host form) the part's text
     // line, word, character and longest-line counts (zarc_gpu_count_batch*): zarc_wc_* over d_vout behind the verdict of a verify pass, per part
     DevBuf d_wc_slices, d_wc_rec, d_wc_out;     // slice prefix; ZarcWcSlice of every slice of the part's grid; ZarcWcFrame of every frame (decoder order)
+    // frames against other bytes (zarc_gpu_compare_batch*): zarc_cmp_* over d_vout and the other sides behind the verdict of a verify pass, per part
+    DevBuf d_cmp_slices, d_cmp_rec, d_cmp_out;  // slice prefix; ZarcCmpSlice of every slice of the part's grid; ZarcCmpFrame of every frame (decoder order)
+    DevBuf d_cmp_off, d_cmp_len;                // where every frame's other side lies and how long it is (decoder order)
+    float cmp_ms = -1.f;        // zarc_cmp_* of the most recent call, summed over its parts (zarc_gpu_last_compare_ms); the timer enum has no entry for it
     bool vout_busy = false;     // a repack pass is between its halves: d_vout is not the check's to take
     uint64_t dec_scratch = 0;   // decoder scratch (sequences, literals, tables) of the most recent decode, as counted against the budget
     // content bytes the most recent batch call moved (zarc_gpu_last_copy_bytes); the copy helpers run on two helper threads
@@ -379,6 +383,7 @@ int check_common(zarc_gpu *h, size_t n)
     if (n > 0x7FFFFFFFu) { set_error(h, "batch too large"); return ZARC_GPU_E_PARAM; }
     ZHIP(hipSetDevice(h->device));
     for (int i = 0; i < ZARC_GPU_T_COUNT; i++) h->ms[i] = -1.f;
+    h->cmp_ms = -1.f;
     h->meta_used = 0; // every batch call ends with its stream synchronised: what the arena held has been copied
     if (!h->nested) for (auto &c : h->copy_bytes) c.store(0, std::memory_order_relaxed);
     return 0;
@@ -582,6 +587,7 @@ const char *zarc_gpu_frame_status_name(int s)
 const char *zarc_gpu_last_error(const zarc_gpu_t *h) { return h ? h->last_error.c_str() : "null handle"; }
 uint64_t zarc_gpu_last_copy_bytes(const zarc_gpu_t *h, int which) { return (h && which >= 0 && which < ZARC_GPU_C_COUNT) ? h->copy_bytes[which].load(std::memory_order_relaxed) : 0; }
 float zarc_gpu_last_kernel_ms(const zarc_gpu_t *h, int which) { return (h && which >= 0 && which < ZARC_GPU_T_COUNT) ? h->ms[which] : -1.f; }
+float zarc_gpu_last_compare_ms(const zarc_gpu_t *h) { return h ? h->cmp_ms : -1.f; }
 
 // ---------------------------------------------------------------------------------------------------
 int zarc_gpu_blake3_batch_device(zarc_gpu_t *h, size_t n, const void *d_base, const uint64_t *off, const uint64_t *len, uint8_t *digest)
@@ -723,7 +729,22 @@ struct WcReq { zarc_gpu_wc *res; }; // host, in the caller's order, this part's 
 WcReq part_of(WcReq r, size_t a) { r.res += a; return r; }
 // what the count kernels keep in the handle's scratch for a part of n frames and `raw` decoded bytes (counted against the budget)
 uint64_t wc_scratch(size_t n, uint64_t raw) { return (raw / ZARC_CHECK_SLICE + n) * sizeof(ZarcWcSlice) + n * sizeof(ZarcWcFrame); }
+// A verify pass that compares what it decoded with other bytes (zarc_gpu_compare_batch*): zarc_cmp_* run behind the verdict, per part, while
+// that part's bytes are in d_vout.  Every pair's answer is its own, so the parts of a call share nothing.
+struct CmpReq {
+    const uint8_t *d_other;               // device: frame i's other side at d_other + other_off[i] (16-byte aligned, padding behind the arena)
+    const uint64_t *other_off, *other_len; // host, in the caller's order, this part's first frame first
+    zarc_gpu_cmp *res;                    // host, the same order
+    bool staged;                          // the host form: the other sides were staged by this call and count against the budget
+};
+struct CmpHost { const void *const *other; const size_t *other_len; zarc_gpu_cmp *res; }; // the host form's request: caller memory, the caller's order
+CmpReq part_of(CmpReq r, size_t a) { r.other_off += a; r.other_len += a; r.res += a; return r; }
+// what the compare kernels keep in the handle's scratch for a part of n frames and `raw` decoded bytes (counted against the budget)
+uint64_t cmp_scratch(size_t n, uint64_t raw) { return (raw / ZARC_CHECK_SLICE + n) * sizeof(ZarcCmpSlice) + n * (sizeof(ZarcCmpFrame) + 16); }
 int lines_text_out(zarc_gpu_t *h, uint8_t *host, const uint8_t *dev, uint64_t bytes);
+static_assert(sizeof(ZarcCmpFrame) == sizeof(zarc_gpu_cmp) && sizeof(zarc_gpu_cmp) == 64 && sizeof(ZarcCmpSlice) == 32, "the device's record is the caller's");
+static_assert(offsetof(ZarcCmpFrame, prefix) == offsetof(zarc_gpu_cmp, prefix) && offsetof(zarc_gpu_cmp, suffix) == 40, "the device's record is the caller's");
+static_assert(ZARC_CMP_R_OTHER_IS_PREFIX == ZARC_GPU_CMP_OTHER_IS_PREFIX && ZARC_CMP_R_DIFFER == ZARC_GPU_CMP_DIFFER && ZARC_CMP_EOF == ZARC_GPU_CMP_EOF, "the device's constants are the caller's");
 static_assert(sizeof(ZarcWcFrame) == sizeof(zarc_gpu_wc) && sizeof(zarc_gpu_wc) == 64, "the device's record is the caller's");
 static_assert(sizeof(ZarcRangeReq) == sizeof(zarc_gpu_range), "the device's range is the caller's");
 static_assert(sizeof(ZarcLineRec) == sizeof(zarc_gpu_line), "the device's record is the caller's");
@@ -731,7 +752,7 @@ static_assert(sizeof(ZarcMatchRec) == sizeof(zarc_gpu_match), "the device's reco
 
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len, void *d_dst_base,
                         const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status, const PackCheck *chk,
-                        const SearchReq *srch = nullptr, const RangeReq *rng = nullptr, const WcReq *wc = nullptr);
+                        const SearchReq *srch = nullptr, const RangeReq *rng = nullptr, const WcReq *wc = nullptr, const CmpReq *cmp = nullptr);
 int check_pack(zarc_gpu_t *h, size_t n, const void *d_src_base, const uint64_t *src_len, void *d_dst, const uint64_t *dst_off, uint64_t *dst_len,
                int *status, bool trailer, const PackPlanned *pl = nullptr);
 void check_message(zarc_gpu_t *h, size_t index);
@@ -1712,11 +1733,52 @@ void wc_deliver(const DecodedPart &p, const WcReq &wc, const WcPart &wp)
     for (size_t i = 0; i < p.n; i++) memcpy(&wc.res[p.order[i]], &wp.out[i], sizeof(zarc_gpu_wc));
 }
 
+// what a part's comparison carries from its launch to its delivery
+struct CmpPart {
+    int c0 = -1, c1 = -1;           // timer marks: in front of the scan, behind the carry
+    std::vector<ZarcCmpFrame> out;  // what cmp_launch asked back (decoder order)
+};
+
+// comparison, first half: the frames are judged; one record per slice, then one zarc_gpu_cmp per frame.  The answers are asked back here and
+// are on the host behind the part's one wait.
+int cmp_launch(const DecodedPart &p, const CmpReq &cmp, CmpPart &cp)
+{
+    zarc_gpu *const h = p.h;
+    const size_t n = p.n;
+    int rc;
+    uint64_t slices = 0;
+    if ((rc = upload_slices(p, h->d_cmp_slices, "compare: batch too large", &slices))) return rc;
+    std::vector<uint64_t> off(n), len(n);
+    for (size_t i = 0; i < n; i++) { off[i] = cmp.other_off[p.order[i]]; len[i] = cmp.other_len[p.order[i]]; }
+    if ((rc = upload_u64(h, h->d_cmp_off, off.data(), n))) return rc;
+    if ((rc = upload_u64(h, h->d_cmp_len, len.data(), n))) return rc;
+    ZHIP(h->d_cmp_rec.reserve(slices * sizeof(ZarcCmpSlice)));
+    ZHIP(h->d_cmp_out.reserve(n * sizeof(ZarcCmpFrame)));
+    const uint64_t *const d_slices = h->d_cmp_slices.as<uint64_t>(), *const d_raw = h->d_raw_len.as<uint64_t>();
+    const uint64_t *const d_ooff = h->d_cmp_off.as<uint64_t>(), *const d_olen = h->d_cmp_len.as<uint64_t>();
+    ZHIP(p.t.mark(&cp.c0));
+    hipLaunchKernelGGL(zarc_cmp_scan, dim3((unsigned)slices), dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw, p.d_status,
+                       cmp.d_other, d_ooff, d_olen, h->d_cmp_rec.as<ZarcCmpSlice>());
+    hipLaunchKernelGGL(zarc_cmp_carry, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (uint32_t)n, d_slices, p.d_base, p.d_off, d_raw,
+                       p.d_status, cmp.d_other, d_ooff, d_olen, h->d_cmp_rec.as<ZarcCmpSlice>(), h->d_cmp_out.as<ZarcCmpFrame>());
+    ZHIP(hipGetLastError());
+    ZHIP(p.t.mark(&cp.c1));
+    cp.out.resize(n);
+    ZHIP(hipMemcpyAsync(cp.out.data(), h->d_cmp_out.p, n * sizeof(ZarcCmpFrame), hipMemcpyDeviceToHost, h->stream));
+    return ZARC_GPU_OK;
+}
+
+// comparison, second half: to the caller's order
+void cmp_deliver(const DecodedPart &p, const CmpReq &cmp, const CmpPart &cp)
+{
+    for (size_t i = 0; i < p.n; i++) memcpy(&cmp.res[p.order[i]], &cp.out[i], sizeof(zarc_gpu_cmp));
+}
+
 // own_out: bytes of engine-owned output scratch this call decodes into (verify, read-back check); they count against the budget
 int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off_in, const uint64_t *frame_len_in,
                        void *d_dst_base, const uint64_t *dst_off_in, const uint64_t *raw_len_in, const uint8_t *expect_in, uint8_t *digest,
                        int *status, uint64_t own_out = 0, const PackCheck *chk = nullptr, DevBuf *order_out = nullptr, const SearchReq *srch = nullptr,
-                       const RangeReq *rng = nullptr, const WcReq *wc = nullptr)
+                       const RangeReq *rng = nullptr, const WcReq *wc = nullptr, const CmpReq *cmp = nullptr)
 {
     int rc = 0;
     h->dec_scratch = 0;
@@ -1886,6 +1948,10 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
         }
         h->dec_scratch = total_seqs * 8 + total_lits + nslots * (uint64_t)(ZDEC_TABLE_CELLS * 2 + sizeof(ZdecBlock) + 32);
         if (wc) h->dec_scratch += wc_scratch(n, total_raw); // the slices' records lie in the handle's scratch beside the decoder's
+        if (cmp) { // ... and so do the other sides the host form staged for this part
+            h->dec_scratch += cmp_scratch(n, total_raw);
+            if (cmp->staged) for (size_t i = 0; i < n; i++) h->dec_scratch += align_up((size_t)cmp->other_len[i], ZARC_GPU_ALIGN);
+        }
         if (h->scratch_budget && n > 1 && own_out + h->dec_scratch > h->scratch_budget) return UNPACK_SPLIT;
         if (!lean) {
             if ((rc = upload_u64(h, h->d_seqidx, seqidx.data(), nslots))) return rc;
@@ -2129,6 +2195,8 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (rng && (rc = range_launch(part, *rng, rp))) return rc;
     WcPart wp;
     if (wc && (rc = wc_launch(part, wp))) return rc;
+    CmpPart cp;
+    if (cmp && (rc = cmp_launch(part, *cmp, cp))) return rc;
     std::vector<int32_t> st_v;
     std::vector<uint8_t> dg_v;
     int32_t *st = (int32_t *)meta_take(h, n * 4); // results come back through the page-locked arena too, then go to the caller's order
@@ -2144,6 +2212,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (srch && srch->lines && (rc = lines_deliver(part, *srch, sp))) return rc;
     if (rng && (rc = range_deliver(part, *rng, rp))) return rc;
     if (wc) wc_deliver(part, *wc, wp);
+    if (cmp) cmp_deliver(part, *cmp, cp);
     if (fastpath && diag_env("ZARC_GPU_DEC_STATS", 0)) { // diagnostics: how many frames had their sequences decoded ahead
         std::vector<uint32_t> fl(n);
         ZHIP(hipMemcpy(fl.data(), h->d_fast.p, n * 4, hipMemcpyDeviceToHost));
@@ -2180,6 +2249,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
     if (srch && srch->lines) { h->ms[ZARC_GPU_T_LINES] = elapsed(h, sp.e6, sp.e7) + sp.lines_ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, sp.e7) + sp.lines_ms2; }
     if (rng) { h->ms[ZARC_GPU_T_RANGE] = elapsed(h, rp.r0, rp.r1) + rp.ms2; h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, rp.r1) + rp.ms2; }
     if (wc) { h->ms[ZARC_GPU_T_WC] = elapsed(h, wp.w0, wp.w1); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, wp.w1); }
+    if (cmp) { h->cmp_ms = elapsed(h, cp.c0, cp.c1); h->ms[ZARC_GPU_T_TOTAL] = elapsed(h, e0, cp.c1); }
     return ZARC_GPU_OK;
 }
 
@@ -2191,7 +2261,7 @@ int unpack_device_once(zarc_gpu_t *h, size_t n, const void *d_frames_base, const
 // that does not fit the device is halved after; a single frame runs alone whatever its size.
 int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
                         void *d_dst_base, const uint64_t *dst_off, const uint64_t *raw_len, const uint8_t *expect, uint8_t *digest, int *status,
-                        const PackCheck *chk = nullptr, const SearchReq *srch, const RangeReq *rng, const WcReq *wc)
+                        const PackCheck *chk = nullptr, const SearchReq *srch, const RangeReq *rng, const WcReq *wc, const CmpReq *cmp)
 {
     const bool own = d_dst_base == nullptr;
     DevBuf &vout = h->vout_busy ? h->d_vout2 : h->d_vout; // (the read-back check inside a repack pass: d_vout holds what it compares with)
@@ -2210,7 +2280,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
     }
     if (attempt)
         rc = unpack_device_once(h, n, d_frames_base, frame_off, frame_len, own ? vout.p : d_dst_base, own ? nullptr : dst_off, raw_len, expect, digest,
-                                status, own_bytes, chk, nullptr, srch, rng, wc);
+                                status, own_bytes, chk, nullptr, srch, rng, wc, cmp);
     if ((rc != UNPACK_SPLIT && rc != ZARC_GPU_E_NOMEM) || n < 2) return rc == UNPACK_SPLIT ? ZARC_GPU_E_NOMEM : rc;
     (void)hipStreamSynchronize(h->stream);
     if (rc == ZARC_GPU_E_NOMEM) {
@@ -2222,7 +2292,7 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
     size_t k = 0;
     while (k + 1 < n && (acc + raw_len[k]) * 2 <= total) acc += raw_len[k++];
     if (k == 0) k = 1;
-    float ms[ZARC_GPU_T_COUNT];
+    float ms[ZARC_GPU_T_COUNT], cmp_ms = 0;
     const size_t part[3] = {0, k, n};
     for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] = 0;
     for (int p = 0; p < 2; p++) {
@@ -2232,13 +2302,16 @@ int unpack_device_split(zarc_gpu_t *h, size_t n, const void *d_frames_base, cons
         const SearchReq ssub = srch ? part_of(*srch, a) : SearchReq{};
         const RangeReq rsub = rng ? part_of(*rng, a) : RangeReq{};
         const WcReq wsub = wc ? part_of(*wc, a) : WcReq{};
+        const CmpReq csub = cmp ? part_of(*cmp, a) : CmpReq{};
         rc = unpack_device_split(h, m, d_frames_base, frame_off + a, frame_len + a, d_dst_base, own ? nullptr : dst_off + a, raw_len + a, expect ? expect + a * 32 : nullptr,
                                  digest ? digest + a * 32 : nullptr, status ? status + a : nullptr, chk ? &sub : nullptr, srch ? &ssub : nullptr, rng ? &rsub : nullptr,
-                                 wc ? &wsub : nullptr);
+                                 wc ? &wsub : nullptr, cmp ? &csub : nullptr);
         if (rc) return rc;
         for (int i = 0; i < ZARC_GPU_T_COUNT; i++) ms[i] += h->ms[i];
+        if (cmp) cmp_ms += h->cmp_ms;
     }
     if (!chk) for (int i = 0; i < ZARC_GPU_T_COUNT; i++) h->ms[i] = ms[i];
+    if (cmp) h->cmp_ms = cmp_ms;
     return ZARC_GPU_OK;
 }
 } // namespace
@@ -2549,6 +2622,25 @@ int zarc_gpu_count_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_ba
     if (!res) { set_error(h, "count: res is needed"); return ZARC_GPU_E_PARAM; }
     const WcReq req{res};
     return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, nullptr, nullptr, &req);
+}
+
+// verify_batch_device with the compare kernels behind every part's verdict; the other sides are where the caller put them
+int zarc_gpu_compare_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
+                                  const uint64_t *raw_len, const uint8_t *expect, const void *d_other_base, const uint64_t *other_off,
+                                  const uint64_t *other_len, uint8_t *digest, int *status, zarc_gpu_cmp *res)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!d_frames_base || !frame_off || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    if ((rc = check_frame_sizes(h, n, frame_len, raw_len))) return rc;
+    if (!res || !d_other_base || !other_off || !other_len) { set_error(h, "compare: res, the other sides, their offsets and lengths are needed"); return ZARC_GPU_E_PARAM; }
+    for (size_t i = 0; i < n; i++) {
+        if (other_len[i] >= 0xFFFFFFF0ull) { set_error(h, "compare: other sides of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
+        if (other_off[i] % ZARC_GPU_ALIGN) { set_error(h, "compare: other offset not 16-byte aligned"); return ZARC_GPU_E_PARAM; }
+    }
+    const CmpReq req{(const uint8_t *)d_other_base, other_off, other_len, res, false};
+    return unpack_device_split(h, n, d_frames_base, frame_off, frame_len, nullptr, nullptr, raw_len, expect, digest, status, nullptr, nullptr, nullptr, nullptr, &req);
 }
 
 int zarc_gpu_search_batch_device(zarc_gpu_t *h, size_t n, const void *d_frames_base, const uint64_t *frame_off, const uint64_t *frame_len,
@@ -3184,20 +3276,29 @@ int zarc_gpu_unpack_batch(zarc_gpu_t *h, size_t n, const void *const *frame, con
 namespace {
 int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                      const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, const SearchReq *srch, const RangeReq *rng = nullptr,
-                     const WcReq *wc = nullptr)
+                     const WcReq *wc = nullptr, const CmpHost *cmp = nullptr)
 {
     int rc = 0;
     if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
     NestedCall nested(h);
     if ((rc = check_frame_sizes(h, n, frame_len, raw_len, frame))) return rc;
-    std::vector<uint64_t> in_sz(n), out_sz(n), weight(n), flen(n), rlen(n);
+    std::vector<uint64_t> in_sz(n), out_sz(n), weight(n), flen(n), rlen(n), olen, oth_sz, up_sz;
     for (size_t i = 0; i < n; i++) {
         flen[i] = frame_len[i]; rlen[i] = raw_len[i];
         in_sz[i] = align_up(frame_len[i], ZARC_GPU_ALIGN);
         out_sz[i] = align_up(raw_len[i], ZARC_GPU_ALIGN);
         weight[i] = std::max(in_sz[i], out_sz[i]);
     }
-    const std::vector<Chunk> cs = make_chunks(n, in_sz, out_sz, weight, h->stage_chunk ? h->stage_chunk : (uint64_t)4 << 30);
+    if (cmp) { // the second staged stream: a chunk's other sides lie in the input arena behind the chunk's frames
+        olen.resize(n); oth_sz.resize(n); up_sz.resize(n);
+        for (size_t i = 0; i < n; i++) {
+            olen[i] = cmp->other_len[i];
+            oth_sz[i] = align_up(cmp->other_len[i], ZARC_GPU_ALIGN);
+            up_sz[i] = in_sz[i] + oth_sz[i];
+            weight[i] = std::max(weight[i], oth_sz[i]);
+        }
+    }
+    const std::vector<Chunk> cs = make_chunks(n, cmp ? up_sz : in_sz, out_sz, weight, h->stage_chunk ? h->stage_chunk : (uint64_t)4 << 30);
     uint64_t max_in = 0;
     for (const Chunk &c : cs) max_in = std::max(max_in, c.in_bytes);
     const uint64_t in_half = align_up(max_in + ZARC_GPU_PAD + 256, 256);
@@ -3209,9 +3310,10 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
         std::vector<Seg> segs;
         uint64_t at = 0;
         for (size_t i = cs[c].i0; i < cs[c].i1; i++) { if (frame_len[i]) segs.push_back(Seg{(uint8_t *)frame[i], at, frame_len[i]}); at += in_sz[i]; }
+        if (cmp) for (size_t i = cs[c].i0; i < cs[c].i1; i++) { if (olen[i]) segs.push_back(Seg{(uint8_t *)cmp->other[i], at, olen[i]}); at += oth_sz[i]; }
         return staged_h2d(h, side, segs, ain + (c & 1) * in_half, at);
     };
-    float sum[ZARC_GPU_T_COUNT] = {};
+    float sum[ZARC_GPU_T_COUNT] = {}, cmp_sum = 0;
     if ((rc = copy_in(0))) return rc;
     ZHIP(hipStreamSynchronize(side));
     for (size_t c = 0; c < cs.size(); c++) {
@@ -3232,16 +3334,25 @@ int verify_host_impl(zarc_gpu_t *h, size_t n, const void *const *frame, const si
         const SearchReq sub = srch ? part_of(*srch, i0) : SearchReq{};
         const RangeReq rsub = rng ? part_of(*rng, i0) : RangeReq{};
         const WcReq wsub = wc ? part_of(*wc, i0) : WcReq{};
+        std::vector<uint64_t> ooff;
+        CmpReq csub{};
+        if (cmp) { // (fa: where the chunk's frames end)
+            ooff.resize(m);
+            for (size_t k = 0; k < m; k++) { ooff[k] = fa; fa += oth_sz[i0 + k]; }
+            csub = CmpReq{ain + (c & 1) * in_half, ooff.data(), olen.data() + i0, cmp->res + i0, true};
+        }
         if (!(rc = check_common(h, m)))
             rc = unpack_device_split(h, m, ain + (c & 1) * in_half, foff.data(), flen.data() + i0, nullptr, nullptr, rlen.data() + i0,
                                      expect ? (const uint8_t *)expect[i0] : nullptr, (uint8_t *)digest[i0], status + i0, nullptr, srch ? &sub : nullptr, rng ? &rsub : nullptr,
-                                     wc ? &wsub : nullptr);
+                                     wc ? &wsub : nullptr, cmp ? &csub : nullptr);
         if (helper.joinable()) helper.join();
         if (rc) return rc;
         if (helper_rc) return helper_rc;
         for (int t = 0; t < ZARC_GPU_T_COUNT; t++) sum[t] += h->ms[t] > 0 ? h->ms[t] : 0;
+        cmp_sum += h->cmp_ms > 0 ? h->cmp_ms : 0;
     }
     for (int t = 0; t < ZARC_GPU_T_COUNT; t++) h->ms[t] = sum[t];
+    if (cmp) h->cmp_ms = cmp_sum;
     return ZARC_GPU_OK;
 }
 
@@ -3298,6 +3409,25 @@ int zarc_gpu_count_batch(zarc_gpu_t *h, size_t n, const void *const *frame, cons
     if (!res) { set_error(h, "count: res is needed"); return ZARC_GPU_E_PARAM; }
     const WcReq req{res};
     return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, nullptr, &req);
+}
+// verify's chunk loop with the compare kernels behind every chunk's verdict: the compressed bytes and the other sides go up, 64 bytes a
+// pair come back
+int zarc_gpu_compare_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
+                           const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *const *other, const size_t *other_len,
+                           uint8_t (*digest)[ZARC_GPU_DIGEST_LEN], int *status, zarc_gpu_cmp *res)
+{
+    int rc = check_common(h, n);
+    if (rc) return rc;
+    if (n == 0) return ZARC_GPU_OK;
+    if (!frame || !frame_len || !raw_len || !digest || !status) return ZARC_GPU_E_PARAM;
+    if ((rc = check_frame_sizes(h, n, frame_len, raw_len, frame))) return rc;
+    if (!res || !other || !other_len) { set_error(h, "compare: res, other and other_len are needed"); return ZARC_GPU_E_PARAM; }
+    for (size_t i = 0; i < n; i++) {
+        if (other_len[i] && !other[i]) { set_error(h, "compare: an other side with bytes has no address"); return ZARC_GPU_E_PARAM; }
+        if ((uint64_t)other_len[i] >= 0xFFFFFFF0ull) { set_error(h, "compare: other sides of 4 GiB or more are not supported"); return ZARC_GPU_E_UNSUPPORTED; }
+    }
+    const CmpHost req{other, other_len, res};
+    return verify_host_impl(h, n, frame, frame_len, raw_len, expect, digest, status, nullptr, nullptr, nullptr, &req);
 }
 int zarc_gpu_search_batch(zarc_gpu_t *h, size_t n, const void *const *frame, const size_t *frame_len, const size_t *raw_len,
                           const uint8_t (*expect)[ZARC_GPU_DIGEST_LEN], const void *pattern, size_t pattern_len, unsigned flags,

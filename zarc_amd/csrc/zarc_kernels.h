@@ -352,6 +352,22 @@ __global__ void zarc_wc_count(uint32_t n, const uint64_t *slice_prefix, const ui
                               const int32_t *status, ZarcWcSlice *rec);
 __global__ void zarc_wc_carry(uint32_t n, const uint64_t *slice_prefix, const uint64_t *raw_len, const int32_t *status, const ZarcWcSlice *rec,
                               ZarcWcFrame *out);
+// the decoded frames against other bytes (zdec_compare.hip); every per-frame array is in the decoder's order.  Frame i's other side lies at
+// oth_base + oth_off[i] (16-byte aligned, padding behind it), oth_len[i] bytes.  ZarcCmpSlice: what zarc_cmp_scan knows of one slice of the
+// part's grid, over the positions below common = min(raw_len, oth_len) -- its differing bytes, the lowest and the highest of them
+// (absolute offsets in the frame; ZARC_CMP_NONE: none), its 0x0A bytes of the frame's side, and those of them in front of `lo`; and, where
+// the lengths differ, the highest position of the slice whose byte is not the one that far from the other side's end (`back`).
+// ZarcCmpFrame is zarc_gpu_cmp.
+constexpr uint32_t ZARC_CMP_NONE = 0xFFFFFFFFu;
+constexpr uint32_t ZARC_CMP_R_NONE = 0, ZARC_CMP_R_EQUAL = 1, ZARC_CMP_R_DIFFER = 2, ZARC_CMP_R_FRAME_IS_PREFIX = 3, ZARC_CMP_R_OTHER_IS_PREFIX = 4; // zarc_gpu_cmp.relation
+constexpr uint32_t ZARC_CMP_EOF = 256; // ZARC_GPU_CMP_EOF
+struct ZarcCmpSlice { uint32_t differing, lo, hi, nls, nl_before, back, pad[2]; };
+struct ZarcCmpFrame { uint32_t relation, byte_a, byte_b, reserved0; uint64_t prefix, line, differing, suffix, reserved[2]; };
+__global__ void zarc_cmp_scan(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                              const int32_t *status, const uint8_t *oth_base, const uint64_t *oth_off, const uint64_t *oth_len, ZarcCmpSlice *rec);
+__global__ void zarc_cmp_carry(uint32_t n, const uint64_t *slice_prefix, const uint8_t *dec_base, const uint64_t *dec_off, const uint64_t *raw_len,
+                               const int32_t *status, const uint8_t *oth_base, const uint64_t *oth_off, const uint64_t *oth_len,
+                               const ZarcCmpSlice *rec, ZarcCmpFrame *out);
 __global__ void zarc_corpus_fill(uint8_t *base, const uint64_t *off, const uint64_t *len, uint32_t n, uint64_t first_index, int kind);
 
 // encoder

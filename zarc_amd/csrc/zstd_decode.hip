@@ -2190,3 +2190,4 @@ __global__ void __launch_bounds__(64) zarc_zdec_literals(const uint8_t *__restri
 #include "zdec_matches.hip" // zarc_matches_*: every match of the delivered lines, cut out where it starts and ends
 #include "zdec_ranges.hip" // zarc_range_*: byte and line ranges of the decoded frames, cut out where they lie
 #include "zdec_wc.hip" // zarc_wc_*: line, word, character and longest-line counts of the decoded frames
+#include "zdec_compare.hip" // zarc_cmp_*: the decoded frames compared with other bytes

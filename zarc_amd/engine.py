@@ -808,6 +808,62 @@ class Engine:
             dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), res))
         return [(bytes(dig[i]), int(status[i])) for i in range(n)], self._wc_result(n, res)
 
+    @staticmethod
+    def _cmp_result(n, res):
+        return [(r.relation, r.prefix, r.line, r.differing, r.suffix, r.byte_a, r.byte_b) for r in res[:n]]
+
+    def compare(self, frames, raw_lens, others, expect=None):
+        """verify() plus what `cmp` says of every frame's content against others[i], compared on the device -> (verdicts, results).
+        verdicts = verify()'s list of (digest, status); results[i] = (relation, prefix, line, differing, suffix, byte_a, byte_b): one of
+        _lib.CMP_*, the offset of the first differing byte (the common length where there is none), 1 + the line feeds of the content
+        in front of it, the number of differing bytes below the common length, the length of the common tail (which never overlaps
+        the common head), and the two bytes at `prefix` (_lib.CMP_EOF where that side ends there); include/zarc_gpu.h has the
+        definitions.  A frame that did not decode gives zeros.  The compressed frames and the other sides cross to the device and 64
+        bytes a pair come back."""
+        n = len(frames)
+        assert len(others) == n
+        bufs = [bytes(f) for f in frames]
+        ptrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in bufs])
+        lens = (ctypes.c_size_t * n)(*[len(b) for b in bufs])
+        obufs = [bytes(o) for o in others]
+        optrs = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in obufs])
+        olens = (ctypes.c_size_t * n)(*[len(b) for b in obufs])
+        rl = (ctypes.c_size_t * n)(*[int(r) for r in raw_lens])
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = (ctypes.c_int * n)()
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(np.frombuffer(b"".join(expect), dtype=np.uint8))
+        res = (_lib.Cmp * max(n, 1))()
+        self._check(self.lib.zarc_gpu_compare_batch(
+            self.h, n, ptrs, lens, rl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None, optrs, olens,
+            dig.ctypes.data_as(ctypes.c_void_p), status, res))
+        return [(bytes(dig[i]), int(status[i])) for i in range(n)], self._cmp_result(n, res)
+
+    def compare_device(self, d_frames, frame_off, frame_len, raw_len, d_other, other_off, other_len, expect=None):
+        """compare() over frames and other sides resident on the device (other_off 16-byte aligned, _lib.PAD readable bytes behind
+        the arena) -> (verdicts, results)"""
+        frame_off, pfo = _u64(frame_off)
+        frame_len, pfl = _u64(frame_len)
+        raw_len, prl = _u64(raw_len)
+        other_off, poo = _u64(other_off)
+        other_len, pol = _u64(other_len)
+        n = len(frame_off)
+        dig = np.zeros((n, 32), dtype=np.uint8)
+        status = np.zeros(n, dtype=np.int32)
+        exp = None
+        if expect is not None:
+            exp = np.ascontiguousarray(expect, dtype=np.uint8)
+        res = (_lib.Cmp * max(n, 1))()
+        self._check(self.lib.zarc_gpu_compare_batch_device(
+            self.h, n, ctypes.c_void_p(d_frames), pfo, pfl, prl, exp.ctypes.data_as(ctypes.c_void_p) if exp is not None else None,
+            ctypes.c_void_p(d_other), poo, pol, dig.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), res))
+        return [(bytes(dig[i]), int(status[i])) for i in range(n)], self._cmp_result(n, res)
+
+    def compare_ms(self):
+        """device time of zarc_cmp_* of the most recent call, summed over its parts; <= 0 after any call but compare"""
+        return float(self.lib.zarc_gpu_last_compare_ms(self.h))
+
     def repack(self, frames, raw_lens, expect=None):
         """-> (new_frames, digests, statuses).  Every frame is judged as verify() judges it; a frame with status 0 is encoded again with
         the handle's current parameters -- the bytes pack() makes of what unpack() delivers -- and every other one gives None.  Only the

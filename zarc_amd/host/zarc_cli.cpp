@@ -182,7 +182,7 @@ bool safe_name(const std::vector<std::string> &name)
 
 int usage()
 {
-    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|grep|cat|wc|list-files> ...\n"
+    std::fprintf(stderr, "usage: zarc [-v...] [--log-file [PATH]] <pack|unpack|verify|repack|grep|cat|wc|compare|list-files> ...\n"
                          "       zarc pack --output PATH [--level N] [--zstd PARAM=VALUE]... [--store] [-L] [--gpus N] [--split-blocks] [--check] PATH...\n"
                          "         --split-blocks  cut 64 KiB blocks where their statistics change (smaller frames on binaries / JSON; off by default)\n"
                          "         --check         decode every frame again on the device and compare it with its file before it is written; a mismatch\n"
@@ -250,6 +250,16 @@ int usage()
                          "         and prints that column as LEN:LINE_NO:OFFSET of the first such line -- the line `zarc cat --lines LINE_NO:LINE_NO` cuts out.\n"
                          "         More than one file: a last line `... total` with the sums and the largest max-line-bytes.  A frame that is not good prints\n"
                          "         a message and no line.  Exit status 0 iff every selected file was counted clean\n"
+                         "       zarc compare [-C DIR | --directory DIR] [--filter REGEX]... [--brief] [--report-identical] [--verify DIGEST] [--gpus N]\n"
+                         "                    [--batch-bytes N] ARCHIVE\n"
+                         "         compares the CONTENT of the regular files (grep's selection) with the files DIR/PATH on disk (DIR: the current directory),\n"
+                         "         on the device, as tar --compare and cmp do; symbolic links, directories, modes, owners and times are not looked at.  The\n"
+                         "         pairs go up in batches of --batch-bytes N (default 268435456) of disk content.  One line per file that is not identical,\n"
+                         "         in directory order: `PATH: differ: byte N, line M, K bytes differ` (N counts from 1, as cmp; where the sizes differ as\n"
+                         "         well: `, sizes A and B, common tail T`), `PATH: archive copy is a prefix: N of B bytes, line M`, `PATH: file is a prefix:\n"
+                         "         N of A bytes, line M`, `PATH: missing`, `PATH: not a regular file`, `PATH: bad frame (STATUS)`, `PATH: unreadable (WHY)`.  --brief\n"
+                         "         prints only PATH; --report-identical adds `PATH: identical`.  An entry whose name would leave DIR is not compared.  Exit\n"
+                         "         status 0: all identical; 1: something differs or is missing; 2: a usage error, a bad frame, an unreadable file or archive\n"
                          "       zarc list-files INPUT [--only-files] [--decorate] [--filter REGEX]...\n");
     return 2;
 }
@@ -1070,6 +1080,156 @@ int cmd_wc(const std::vector<std::string> &a)
     return failed ? 1 : 0;
 }
 
+// the work of `zarc compare` behind its options; a zarc::Error leaves through cmd_compare
+int compare_run(const std::string &input, const std::string &verify, const std::string &dir, const std::vector<std::regex> &filters, int gpus, bool brief,
+                bool identical, uint64_t batch_bytes)
+{
+    Mapped m(input);
+    std::vector<int> devices;
+    for (int d = 0; d < gpus; d++) devices.push_back(d);
+    zarc::ArchiveReader rd(m.p, m.n, devices);
+    const std::string digest = base64(rd.trailer().digest.bytes.data(), 32);
+    if (!verify.empty()) {
+        if (verify != digest) { std::fprintf(stderr, "Error: integrity failure: zarc file digest is %s\n", digest.c_str()); return 2; }
+    } else std::fprintf(stderr, "digest: %s\n", digest.c_str());
+    unsigned long long n_files = 0, n_same = 0, n_differ = 0, n_missing = 0, n_bad = 0;
+    // a file's turn: a line that is known without the device, or the pair it waits for
+    struct Turn { std::string path, line; size_t pair; };
+    std::vector<Turn> turns;
+    std::vector<zarc::Digest> batch;
+    std::vector<std::vector<uint8_t>> disk;
+    uint64_t weight = 0;
+    auto say = [&](const std::string &path, const std::string &what) { std::fprintf(stdout, brief ? "%s\n" : "%s: %s\n", path.c_str(), what.c_str()); };
+    auto flush = [&]() {
+        std::vector<zarc::FrameReader::Result> res;
+        if (!batch.empty()) {
+            std::vector<zarc::FrameReader::Other> others;
+            for (const auto &d : disk) others.push_back(zarc::FrameReader::Other{d.empty() ? nullptr : d.data(), d.size()});
+            res = rd.compare_frames(batch, others);
+            LOGF(3, "compare_frames", "pairs=%zu bytes=%llu", batch.size(), (unsigned long long)weight);
+        }
+        for (const Turn &t : turns) {
+            if (!t.line.empty()) { say(t.path, t.line); continue; }
+            const zarc::FrameReader::Result &r = res[t.pair];
+            const bool decoded = r.status == ZARC_GPU_FRAME_OK || r.status == ZARC_GPU_FRAME_DIGEST;
+            if (!decoded || !r.verify.value_or(false)) { // verify's words
+                say(t.path, std::string("bad frame (") + (decoded ? "frame verification failed!" : zarc_gpu_frame_status_name(r.status)) + ")");
+                n_bad++;
+                continue;
+            }
+            const zarc::FrameReader::Result::Compare &c = r.cmp;
+            const unsigned long long la = rd.frames().at(batch[t.pair]).uncompressed, lb = disk[t.pair].size();
+            const std::string line = ", line " + std::to_string(c.line);
+            switch (c.relation) {
+            case ZARC_GPU_CMP_EQUAL:
+                n_same++;
+                if (identical) say(t.path, "identical");
+                break;
+            case ZARC_GPU_CMP_DIFFER: {
+                std::string s = "differ: byte " + std::to_string(c.prefix + 1) + line + ", " + std::to_string(c.differing) + " bytes differ";
+                if (la != lb) s += ", sizes " + std::to_string(la) + " and " + std::to_string(lb) + ", common tail " + std::to_string(c.suffix);
+                say(t.path, s);
+                n_differ++;
+                break;
+            }
+            case ZARC_GPU_CMP_FRAME_IS_PREFIX:
+                say(t.path, "archive copy is a prefix: " + std::to_string(la) + " of " + std::to_string(lb) + " bytes" + line);
+                n_differ++;
+                break;
+            case ZARC_GPU_CMP_OTHER_IS_PREFIX:
+                say(t.path, "file is a prefix: " + std::to_string(lb) + " of " + std::to_string(la) + " bytes" + line);
+                n_differ++;
+                break;
+            default:
+                say(t.path, "bad frame (no result)");
+                n_bad++;
+            }
+        }
+        turns.clear();
+        batch.clear();
+        disk.clear();
+        weight = 0;
+    };
+    // the selection is grep's: regular files that pass the filters, in directory order
+    for (size_t i = 0; i < rd.files().size(); i++) {
+        const zarc::File &f = rd.files()[i];
+        const std::string path = to_path(f.name);
+        if (!f.is_normal() || !passes(filters, path)) continue;
+        n_files++;
+        if (!rd.frames().count(*f.digest)) { turns.push_back(Turn{path, "bad frame (frame not found)", 0}); n_bad++; continue; }
+        // (an entry name is untrusted, as in unpack: nothing outside DIR is looked at)
+        if (!safe_name(f.name)) { turns.push_back(Turn{path, "unsafe pathname, not compared", 0}); n_bad++; continue; }
+        const std::string on_disk = dir + "/" + path;
+        struct stat st;
+        if (lstat(on_disk.c_str(), &st) != 0) {
+            if (errno == ENOENT || errno == ENOTDIR) { turns.push_back(Turn{path, "missing", 0}); n_missing++; }
+            else { turns.push_back(Turn{path, std::string("unreadable (") + std::strerror(errno) + ")", 0}); n_bad++; }
+            continue;
+        }
+        if (!S_ISREG(st.st_mode)) { turns.push_back(Turn{path, "not a regular file", 0}); n_differ++; continue; }
+        if ((uint64_t)st.st_size >= 0xFFFFFFF0ull) { turns.push_back(Turn{path, "unreadable (files of 4 GiB or more are not supported)", 0}); n_bad++; continue; }
+        std::vector<uint8_t> bytes((size_t)st.st_size);
+        const int fd = open(on_disk.c_str(), O_RDONLY);
+        size_t got = 0;
+        int read_errno = fd >= 0 ? 0 : errno;
+        while (!read_errno && got < bytes.size()) {
+            const ssize_t k = read(fd, bytes.data() + got, bytes.size() - got);
+            if (k < 0 && errno == EINTR) continue;
+            if (k < 0) { read_errno = errno; break; }
+            if (k == 0) break; // (a file that shrank meanwhile is what was read of it)
+            got += (size_t)k;
+        }
+        if (fd >= 0) close(fd);
+        if (read_errno) { turns.push_back(Turn{path, std::string("unreadable (") + std::strerror(read_errno) + ")", 0}); n_bad++; continue; }
+        bytes.resize(got);
+        turns.push_back(Turn{path, "", batch.size()});
+        batch.push_back(*f.digest);
+        weight += bytes.size();
+        disk.push_back(std::move(bytes));
+        if (weight >= batch_bytes) flush();
+    }
+    flush();
+    std::fflush(stdout);
+    std::fprintf(stderr, "compared %llu files: %llu identical, %llu differ, %llu missing, %llu failed\n", n_files, n_same, n_differ, n_missing, n_bad);
+    return n_bad ? 2 : (n_differ || n_missing) ? 1 : 0;
+}
+
+// `zarc compare`: is the tree on disk still what was packed, and where does it differ?  The content of every regular file that passes the
+// filters is decoded and judged on the device and compared there with the bytes of DIR/PATH (zarc_gpu_compare_batch): the frames and the
+// disk content go up, 64 bytes a pair come back.  A frame that several files share is one pair per file.  Content only: no symbolic
+// links, directories, modes, owners or times.  Nothing is created or changed in the file system.
+int cmd_compare(const std::vector<std::string> &a)
+{
+    std::string input, verify, dir = ".";
+    std::vector<std::regex> filters;
+    int gpus = 1;
+    bool brief = false, identical = false;
+    uint64_t batch_bytes = (uint64_t)256 << 20;
+    for (size_t i = 0; i < a.size(); i++) {
+        const bool value = i + 1 < a.size();
+        if (a[i] == "--filter" && value) filters.emplace_back(a[++i]);
+        else if (a[i] == "--verify" && value) verify = a[++i];
+        else if (a[i] == "--gpus" && value) gpus = std::atoi(a[++i].c_str());
+        else if ((a[i] == "-C" || a[i] == "--directory") && value) dir = a[++i];
+        else if (a[i] == "--brief") brief = true;
+        else if (a[i] == "--report-identical") identical = true;
+        else if (a[i] == "--batch-bytes" && value) { if (!cat_number(a[++i], &batch_bytes) || batch_bytes < 1) return usage(); }
+        else if (!a[i].empty() && a[i][0] == '-') return usage();
+        else if (!input.empty()) return usage();
+        else input = a[i];
+    }
+    if (input.empty() || dir.empty() || gpus < 1 || gpus > 64) return usage();
+    if (gpus > zarc_gpu_device_count()) { std::fprintf(stderr, "Error: --gpus %d but %d device(s) are usable\n", gpus, zarc_gpu_device_count()); return 2; }
+    // exit status 1 means "something differs": an archive that cannot be read or an engine error is trouble, 2, with what was found so far
+    try {
+        return compare_run(input, verify, dir, filters, gpus, brief, identical, batch_bytes);
+    } catch (const zarc::Error &e) {
+        std::fflush(stdout);
+        std::fprintf(stderr, "Error: %s\n", e.what());
+        return 2;
+    }
+}
+
 // `zarc grep`: which files contain this byte string?  Every distinct content frame behind the files that pass the filters is decoded,
 // judged and searched on the device (zarc_gpu_search_batch; with -e / -f / --tally a set of strings in one pass, zarc_gpu_search_set_batch;
 // with -E a regular expression, zarc_gpu_search_regex_batch):
@@ -1542,7 +1702,7 @@ int main(int argc, char **argv)
         else if (a == "--log-file") {
             have_log_file = true;
             // num_args = 0..=1: a following word that is not a subcommand is the path
-            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0 || std::string("grep").rfind(n, 0) == 0 || std::string("cat").rfind(n, 0) == 0 || std::string("wc").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
+            if (i + 1 < argc) { const std::string n = argv[i + 1]; const bool verb = !n.empty() && (std::string("pack").rfind(n, 0) == 0 || std::string("unpack").rfind(n, 0) == 0 || std::string("list-files").rfind(n, 0) == 0 || std::string("verify").rfind(n, 0) == 0 || std::string("repack").rfind(n, 0) == 0 || std::string("grep").rfind(n, 0) == 0 || std::string("cat").rfind(n, 0) == 0 || std::string("wc").rfind(n, 0) == 0 || std::string("compare").rfind(n, 0) == 0); if (!verb && n[0] != '-') log_file = argv[++i]; }
         } else break;
     }
     if (i >= argc) return usage();
@@ -1559,6 +1719,7 @@ int main(int argc, char **argv)
         if (!verb.empty() && std::string("grep").rfind(verb, 0) == 0) return cmd_grep(rest);
         if (!verb.empty() && std::string("cat").rfind(verb, 0) == 0) return cmd_cat(rest);
         if (!verb.empty() && std::string("wc").rfind(verb, 0) == 0) return cmd_wc(rest);
+        if (!verb.empty() && std::string("compare").rfind(verb, 0) == 0) return cmd_compare(rest);
         return usage();
     } catch (const zarc::Error &e) {
         std::fprintf(stderr, "Error: %s\n", e.what());

@@ -567,6 +567,20 @@ class ArchiveReader {
         for (size_t i = 0; i < digests.size(); i++) out.push_back(got[slot[i]]);
         return out;
     }
+    // check_frames plus what `cmp` says of every frame's content against others[i], compared on the device
+    // (FrameReader::compare_content_frames): per pair, in order, `cmp`.  A frame that several files refer to is one pair per file: every
+    // pair has its own other side.
+    std::vector<FrameReader::Result> compare_frames(const std::vector<Digest> &digests, const std::vector<FrameReader::Other> &others)
+    {
+        if (others.size() != digests.size()) throw Error(ZARC_GPU_E_PARAM, "compare: one other side per digest is needed");
+        std::vector<Frame> wanted;
+        for (const Digest &d : digests) {
+            auto it = frames_.find(d);
+            if (it == frames_.end()) throw Error(ZARC_GPU_E_PARAM, "digest has no frame");
+            wanted.push_back(it->second);
+        }
+        return reader_.compare_content_frames(data_, len_, wanted, others);
+    }
     // ... for every frame of the directory, in the order of frames()
     std::vector<FrameReader::Result> check_frames()
     {

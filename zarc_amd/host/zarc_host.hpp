@@ -405,7 +405,12 @@ class FrameReader {
         // count_content_frames: zarc_gpu_wc's six fields; all zero for a frame that did not decode
         struct Count { uint64_t lines = 0, words = 0, chars = 0, max_line = 0, max_line_start = 0, max_line_no = 0; };
         Count wc;
+        // compare_content_frames: zarc_gpu_cmp's fields; all zero (relation ZARC_GPU_CMP_NONE) for a frame that did not decode
+        struct Compare { uint32_t relation = 0, byte_a = 0, byte_b = 0; uint64_t prefix = 0, line = 0, differing = 0, suffix = 0; };
+        Compare cmp;
     };
+    // the other side of a pair of compare_content_frames: caller memory; data may be null where len is 0
+    struct Other { const void *data = nullptr; size_t len = 0; };
     explicit FrameReader(int device = 0) : FrameReader(std::vector<int>{device}) {}
     explicit FrameReader(const std::vector<int> &devices)
     {
@@ -685,6 +690,57 @@ class FrameReader {
         else {
             std::vector<std::thread> th;
             for (size_t d = 0; d < g; d++) th.emplace_back(count_share, d);
+            for (auto &t : th) t.join();
+        }
+        for (size_t d = 0; d < g; d++) engines_[d]->check(rc[d]);
+        return out;
+    }
+
+    // check_content_frames plus what `cmp` says of every frame's content against others[i], compared on the device
+    // (zarc_gpu_compare_batch): per pair {digest, verify, status} and `cmp`.  wanted[i] and others[i] are one pair; a frame may stand in
+    // several pairs.  The same dealing over the handles, one thread per handle; every pair's answer is its own, so the results are in the
+    // caller's order and identical for every number of handles.  The frames and the other sides go up; 64 bytes a pair come back.
+    std::vector<Result> compare_content_frames(const uint8_t *archive, size_t archive_len, const std::vector<Frame> &wanted, const std::vector<Other> &others)
+    {
+        const size_t n = wanted.size();
+        if (others.size() != n) throw Error(ZARC_GPU_E_PARAM, "compare: one other side per frame is needed");
+        std::vector<Result> out(n);
+        check_frame_records(archive_len, wanted);
+        if (n == 0) return out;
+        std::vector<size_t> rl(n);
+        for (size_t i = 0; i < n; i++) rl[i] = std::max<size_t>(wanted[i].uncompressed, others[i].len);
+        const size_t g = engines_.size();
+        const auto share = shard_assign(rl.data(), n, g);
+        std::vector<int> rc(g, ZARC_GPU_OK);
+        auto compare_share = [&](size_t d) {
+            const std::vector<size_t> &idx = share[d];
+            const size_t m = idx.size();
+            if (m == 0) return;
+            std::vector<const void *> fp(m), op(m);
+            std::vector<size_t> fl(m), ul(m), ol(m);
+            std::vector<Digest> expect(m), got(m);
+            std::vector<int> status(m);
+            std::vector<zarc_gpu_cmp> res(m);
+            for (size_t j = 0; j < m; j++) {
+                const Frame &f = wanted[idx[j]];
+                fp[j] = archive + f.offset; fl[j] = f.length; ul[j] = f.uncompressed; expect[j] = f.digest;
+                op[j] = others[idx[j]].data; ol[j] = others[idx[j]].len;
+            }
+            rc[d] = zarc_gpu_compare_batch(engines_[d]->get(), m, fp.data(), fl.data(), ul.data(), (const uint8_t(*)[32])expect.data(), op.data(), ol.data(),
+                                           (uint8_t(*)[32])got.data(), status.data(), res.data());
+            if (rc[d] != ZARC_GPU_OK) return;
+            for (size_t j = 0; j < m; j++) {
+                Result &r = out[idx[j]];
+                r.status = status[j];
+                r.digest = got[j];
+                if (status[j] == ZARC_GPU_FRAME_OK || status[j] == ZARC_GPU_FRAME_DIGEST) r.verify = got[j] == expect[j];
+                r.cmp = Result::Compare{res[j].relation, res[j].byte_a, res[j].byte_b, res[j].prefix, res[j].line, res[j].differing, res[j].suffix};
+            }
+        };
+        if (g == 1) compare_share(0);
+        else {
+            std::vector<std::thread> th;
+            for (size_t d = 0; d < g; d++) th.emplace_back(compare_share, d);
             for (auto &t : th) t.join();
         }
         for (size_t d = 0; d < g; d++) engines_[d]->check(rc[d]);
